@@ -202,6 +202,38 @@ struct SuppAd {
 
 };
 
+// the same model in an outputs-only launch (dense output, SuppArgs::T_data > 0): u0 from the data's first column, the
+// states written at the output times, no residual (forward only); NaN throughout for a subject with a non-finite input
+template <int W, int D, int HA = kActHiddenTanh, int OA = kActOutSoftplus>
+struct SuppAdOut : SuppAd<W, D, HA, OA> {
+    using Base = SuppAd<W, D, HA, OA>;
+    using typename Base::Net;
+    using typename Base::Args;
+    using Base::NS;
+    bool bad;
+    __device__ __forceinline__ double init(const Args& a, double*, int, int64_t i, int64_t set, double (&y)[NS]) {
+        this->p = as_const(a.nn + set * a.set_stride_nn);
+        double cst[1] = {exp(a.cond[set * a.set_stride_cond + i])};
+        Net::first_layer_offset(this->p, cst, this->c);
+        double chk = fma(cst[0], 0.0, Net::param_check(this->p));
+#pragma unroll
+        for (int s = 0; s < 3; s++) {
+            y[s] = a.data[((int64_t)s * a.T_data + 0) * a.N + i];
+            chk = fma(y[s], 0.0, chk);
+        }
+        bad = !(chk == 0.0);
+        return chk;
+    }
+    __device__ __forceinline__ double residual2(const Args& a, int oi, int64_t i, const double (&o)[NS], bool active) const {
+        if (active) {
+            double* tr = a.traj + oi * a.traj_st + i * a.traj_sn;
+#pragma unroll
+            for (int s = 0; s < 3; s++) tr[s * a.traj_ss] = bad ? __builtin_nan("") : o[s];
+        }
+        return 0.0;
+    }
+};
+
 __device__ __forceinline__ double rms(const double* v, int n) {
     double s = 0.0;
     for (int k = 0; k < n; k++) s = fma(v[k], v[k], s);

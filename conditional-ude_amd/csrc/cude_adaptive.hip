@@ -522,6 +522,16 @@ static hipError_t launch_adaptive(const typename M::Args& a, int extra_rows, boo
     return hipGetLastError();
 }
 
+// outputs-only launch of the suppression model (dense output, SuppArgs::T_data > 0; M = SuppAdOut): forward only
+template <class M>
+static hipError_t launch_adaptive_out(const SuppArgs& a, hipStream_t s) {
+    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const size_t lds = sizeof(double) * (size_t)adaptive_rows<M>(false) * kBlock;
+    if (a.traj == nullptr || a.n_sets > 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((adaptive_kernel<M, false, false>), dim3((unsigned)nblocks), dim3(kBlock), lds, s, a);
+    return hipGetLastError();
+}
+
 #ifndef CUDE_AD_PART
 #define CUDE_AD_PART 0
 #endif
@@ -545,7 +555,9 @@ static hipError_t launch_cpep_adaptive_general(const NetShape& net, bool grad, c
 }
 template <int W, int D>
 static hipError_t launch_supp_adaptive_general(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_adaptive<SuppAd<W, D, HA, OA>, false>(a, 0, grad, s);
+#define Y(HA, OA)                                                                                                        \
+    if (net.hact == HA && net.oact == OA)                                                                                \
+        return a.T_data > 0 ? launch_adaptive_out<SuppAdOut<W, D, HA, OA>>(a, s) : launch_adaptive<SuppAd<W, D, HA, OA>, false>(a, 0, grad, s);
     CUDE_GENERAL_ACTS(Y)
 #undef Y
     return hipErrorInvalidValue;
@@ -581,7 +593,7 @@ hipError_t launch_cpep_adaptive(const NetShape& net, bool grad, const CpepArgs& 
 }
 
 hipError_t launch_supp_adaptive(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
-    if (net.nin != 4 || a.T < 1) return hipErrorInvalidValue;
+    if (net.nin != 4 || a.T < 1 || (a.T_data > 0 && grad)) return hipErrorInvalidValue;
 #ifndef CUDE_ADAPT_ONE_BODY
     if (!net.general()) {
         const hipError_t e = launch_supp_adaptive_unrolled(net, grad, a, s);
@@ -594,7 +606,9 @@ hipError_t launch_supp_adaptive(const NetShape& net, bool grad, const SuppArgs& 
 #undef X
         return hipErrorInvalidValue;
     }
-#define X(W, D) if (net.width == W && net.depth == D) return launch_adaptive<SuppAd<W, D>, false>(a, 0, grad, s);
+#define X(W, D)                                                                                                          \
+    if (net.width == W && net.depth == D)                                                                                \
+        return a.T_data > 0 ? launch_adaptive_out<SuppAdOut<W, D>>(a, s) : launch_adaptive<SuppAd<W, D>, false>(a, 0, grad, s);
     CUDE_SUPP_AD_SHAPES(X)
 #undef X
     return hipErrorInvalidValue;

@@ -353,9 +353,21 @@ static hipError_t launch_unrolled_supp(const SuppArgs& a, bool grad, hipStream_t
     return hipGetLastError();
 }
 
+// outputs-only launch (dense output, SuppArgs::T_data > 0; M = SuppAdOut): forward only
+template <class M>
+static hipError_t launch_unrolled_supp_out(const SuppArgs& a, hipStream_t s) {
+    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const size_t lds = sizeof(double) * (size_t)kRedRows * kBlock;
+    if (a.traj == nullptr || a.n_sets > 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((adaptive_unrolled_supp_kernel<M, false>), dim3((unsigned)nblocks), dim3(kBlock), lds, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_supp_adaptive_unrolled(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
     if (net.general() || net.nin != 4 || a.T < 1) return hipErrorNotSupported;
-#define X(W, D) if (net.width == W && net.depth == D) return launch_unrolled_supp<SuppAd<W, D>>(a, grad, s);
+#define X(W, D)                                                                                                          \
+    if (net.width == W && net.depth == D)                                                                                \
+        return a.T_data > 0 ? launch_unrolled_supp_out<SuppAdOut<W, D>>(a, s) : launch_unrolled_supp<SuppAd<W, D>>(a, grad, s);
     CUDE_SUPP_AD_UNROLLED(X)
 #undef X
     return hipErrorNotSupported;

@@ -150,6 +150,11 @@ void interp_weights(double th, double* w) {
     for (int i = 0; i < 7; i++) w[i] = ((TR[i][3] * th + TR[i][2]) * th + TR[i][1]) * th * th + TR[i][0] * th;
 }
 
+void supp_output_rho(int S, double h, const std::vector<int32_t>& step, const std::vector<double>& w, std::vector<double>& obs_rho) {
+    std::vector<double> rho;
+    linear_state_tables(S, h, step, w, rho, obs_rho);
+}
+
 
 }  // namespace api
 }  // namespace cude
@@ -200,6 +205,8 @@ const OptionEntry kOptions[] = {
     {"graph", "CUDE_NO_GRAPH", &Options::graph, true, true},
     {"graph_unroll", "CUDE_GRAPH_UNROLL", &Options::graph_unroll, false, true},
     {"prio_shift", "CUDE_PRIO_SHIFT", &Options::prio_shift, false, true},
+    {"dense_chunk", "CUDE_DENSE_CHUNK", &Options::dense_chunk, false, false},
+    {"dense_layout", "CUDE_DENSE_LAYOUT", &Options::dense_layout, false, false},
 };
 }  // namespace
 

@@ -84,6 +84,9 @@ struct Options {
                                 //   peers sit on other devices (the owner's polls may then be served from its L2)
     int xchg_fail_kinds = 0;    // "xchg_fail_kinds" / CUDE_XCHG_FAIL_KINDS (tests): bit k set = this rank's cude_xchg_attach
                                 //   reports a failure when its mailbox is of the k-th memory kind (0 uncached, 1 fine-grained, 2 plain)
+    int dense_chunk = 0;        // "dense_chunk" / CUDE_DENSE_CHUNK: cude_simulate's output times per launch (0 = ~1 GB of scratch)
+    int dense_layout = 0;       // "dense_layout" / CUDE_DENSE_LAYOUT: suppression dense output written straight into the caller's
+                                //   [3 x T x N] (0, measured faster: cude_simulate) or lane-contiguous [T][3][N] + a transpose (1)
     // ("hidden_activation" = tanh | relu | sigmoid, "output_activation" = softplus | identity: kept in cude_ctx::net)
     // ---- ablation
     int mixed = 1;              // CUDE_NO_MIXED
@@ -259,6 +262,8 @@ inline int32_t bind(cude_ctx* c) {
 
 // ---- cude_context.hip
 void interp_weights(double theta, double* w7);      // h-free dense-output weights b_i(theta) of Tsit5
+// suppression model, fixed step: state 1 at outputs (step[k], w[k][0..6]) relative to u1(t_0) (SuppArgs::obs_rho)
+void supp_output_rho(int S, double h, const std::vector<int32_t>& step, const std::vector<double>& w, std::vector<double>& obs_rho);
 int32_t apply_option(cude_ctx* c, const char* name, const char* value);
 // ---- cude_launch.hip
 cude::CpepArgs cpep_args(const cude_ctx* c);

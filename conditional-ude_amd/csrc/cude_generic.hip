@@ -247,6 +247,34 @@ struct GenSupp {
     }
 };
 
+// the same model in an outputs-only launch (dense output, SuppArgs::T_data > 0): u0 from the data's first column, the
+// states written at the output times, no residual (forward only); NaN throughout for a subject with a non-finite input
+struct GenSuppOut : GenSupp {
+    bool bad;
+    __device__ __forceinline__ double init(const Args& a, const GenNet& net, const GenLds& s, int64_t i_, int64_t set, double (&y)[NS]) {
+        i = i_; N = a.N;
+        et = exp(a.cond[set * a.set_stride_cond + i]);
+        s.col[3 * kBlock] = et;
+        double chk = et * 0.0;
+        for (int q = 0; q < 3; q++) {
+            y[q] = a.data[((int64_t)q * a.T_data + 0) * N + i];
+            chk = fma(y[q], 0.0, chk);
+        }
+        double pchk = chk;
+        for (int q = 0; q < net.n_params(); q++) pchk = fma(s.w[q], 0.0, pchk);      // (the weights are staged already)
+        bad = !(pchk == 0.0);
+        base = 0.0;
+        return chk;
+    }
+    __device__ __forceinline__ double residual2(const Args& a, int oi, const double (&o)[NS], bool active) const {
+        if (active) {
+            double* tr = a.traj + oi * a.traj_st + i * a.traj_sn;
+            for (int q = 0; q < 3; q++) tr[q * a.traj_ss] = bad ? __builtin_nan("") : o[q];
+        }
+        return 0.0;
+    }
+};
+
 // ---------------------------------------------------------------------------------- the integrator
 template <class M, bool GRAD>
 __global__ __launch_bounds__(kBlock) void generic_kernel(typename M::Args a, GenNet net) {
@@ -544,6 +572,19 @@ hipError_t launch_generic(const GenNet& net, bool grad, const typename M::Args& 
     return hipGetLastError();
 }
 
+template <class M>
+hipError_t launch_generic_out(const GenNet& net, const typename M::Args& a, hipStream_t s) {
+    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const size_t lds = gen_lds_bytes(net);
+    if (lds > kGenMaxLds || a.traj == nullptr || a.n_sets > 1) return hipErrorInvalidValue;
+    hipError_t e;
+    if (lds > 65536 &&
+        (e = hipFuncSetAttribute((const void*)generic_kernel<M, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((generic_kernel<M, false>), dim3((unsigned)nblocks), dim3(kBlock), lds, s, a, net);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 size_t gen_lds_bytes(const GenNet& net) {
@@ -562,6 +603,7 @@ hipError_t launch_cpep_generic(const NetShape& net, int n_state, bool grad, cons
 
 hipError_t launch_supp_generic(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
     if (!net.generic() || net.gen.nin != 4) return hipErrorInvalidValue;
+    if (a.T_data > 0) return grad ? hipErrorInvalidValue : launch_generic_out<GenSuppOut>(net.gen, a, s);
     return launch_generic<GenSupp>(net.gen, grad, a, s);
 }
 

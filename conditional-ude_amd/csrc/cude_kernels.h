@@ -253,6 +253,11 @@ struct SuppArgs {
     int32_t* tape_n;
     double* gen_acc;         // as CpepArgs
     const int32_t* perm;     // as CpepArgs
+    // outputs-only launches (dense output, cude_simulate), selected by T_data > 0: T counts the output times (obs_step /
+    // obs_w / obs_rho or out_times hold T entries), T_data is the time stride of `data`, whose first column is u0.  No
+    // residual, no SSE, no partials: the states go to traj[s * traj_ss + oi * traj_st + i * traj_sn] (subject i).
+    int32_t T_data;
+    int64_t traj_ss, traj_st, traj_sn;
 };
 
 // the fallback kernel for networks no tuned kernel is compiled for (net.generic(); cude_generic.hip)
@@ -261,6 +266,10 @@ hipError_t launch_supp_generic(const NetShape& net, bool grad, const SuppArgs& a
 // returns hipSuccess, or hipErrorInvalidValue when the shape is not compiled in
 hipError_t launch_cpep(const NetShape& net, int n_state, bool grad, const CpepArgs& a, hipStream_t s);
 hipError_t launch_supp(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s);
+// outputs-only launch of the fixed-step tuned kernels (SuppArgs::T_data > 0; cude_supp_dense.hip); launch_supp routes here
+hipError_t launch_supp_dense(const NetShape& net, const SuppArgs& a, hipStream_t s);
+// [T][3][N] (lane-contiguous dense output) -> [N][T][3] (the column-major [3 x T x N] of the caller)
+hipError_t launch_supp_traj_transpose(int64_t N, int T, const double* src, double* dst, hipStream_t s);
 bool cpep_shape_supported(const NetShape& net, int n_state);
 bool supp_shape_supported(const NetShape& net);
 int supp_grad_waves_per_cu(const NetShape& net);

@@ -800,11 +800,11 @@ int32_t cude_loss_grad(cude_ctx* c, double* loss, double* g_nn, double* g_cond) 
 int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double* traj) {
     int32_t rc = bind(c);
     if (rc) return rc;
-    if (!is_cpep(c)) return fail(CUDE_ERR_UNSUPPORTED, "cude_simulate: c-peptide models only");
     if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
     if (!c->have_nn || !c->have_cond) return fail(CUDE_ERR_STATE, "parameters not set");
     if (n_times < 1 || !times || !traj) return fail(CUDE_ERR_ARG, "null/empty input");
-    const int S = c->cfg.n_steps, NS = c->cfg.n_state;
+    const bool cpep = is_cpep(c);
+    const int S = c->cfg.n_steps, NS = cpep ? c->cfg.n_state : 3;
     const double t0 = c->tp.front(), t1 = c->tp.back(), h = adaptive(c) ? (t1 - t0) : (t1 - t0) / S;
     for (int i = 0; i < n_times; i++) {
         if (!(times[i] >= t0 - 1e-9 * h && times[i] <= t1 + 1e-9 * h))
@@ -813,20 +813,35 @@ int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double*
     }
     const int64_t N = c->N;
     // output times per launch: ~1 GB of trajectory scratch at most (every launch integrates from t_0 again)
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_times, (int64_t)(1e9 / (8.0 * NS * (double)N))));
-    DevBuf<double> d_traj, d_w, d_times;
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_times, (int64_t)(1e9 / (8.0 * NS * (double)N))));
+    if (c->opt.dense_chunk > 0) chunk = std::min<int64_t>(chunk, c->opt.dense_chunk);
+    // suppression model: the kernels write the caller's [3 x T x N] directly (8-byte stores 24 T bytes apart between the
+    // lanes of a wave; L2 merges a lane's consecutive outputs) or, option "dense_layout" = 1, lane-contiguous rows
+    // [T][3][N] (one 512-byte store per state, output time and wave) that a transpose kernel reorders.  Measured at 1e5
+    // subjects, 301 times, 4-3x5-1 (cude_forward at the 8 data times: 0.40 / 0.41 ms): direct 0.56-0.72 ms (fixed step) /
+    // 0.80-0.82 ms (adaptive) against rows 0.54-0.68 + 0.41-0.45 ms transpose / 1.13-1.15 + 0.41-0.46 ms -- the direct
+    // stores are not the bottleneck, so they are the default.  The call itself (~365 ms) is host-side copying.
+    const bool rows = !cpep && c->opt.dense_layout == 1;
+    DevBuf<double> d_traj, d_rows, d_w, d_times, d_rho;
     DevBuf<int32_t> d_step;
     HIP_TRY(d_traj.resize((size_t)NS * chunk * N));
+    if (rows) HIP_TRY(d_rows.resize((size_t)NS * chunk * N));
     HIP_TRY(d_w.resize((size_t)chunk * 7));
     HIP_TRY(d_step.resize((size_t)chunk));
     HIP_TRY(d_times.resize((size_t)chunk));
+    if (!cpep) HIP_TRY(d_rho.resize((size_t)chunk));
     std::vector<int32_t> step(chunk);
-    std::vector<double> w((size_t)chunk * 7);
+    std::vector<double> w((size_t)chunk * 7), rho;
     for (int64_t k0 = 0; k0 < n_times; k0 += chunk) {
         const int64_t kn = std::min<int64_t>(chunk, n_times - k0);
+        double* const dst = rows ? d_rows.p : d_traj.p;          // what the solve writes
         if (adaptive(c)) {                                  // the kernel interpolates at the times themselves
             HIP_TRY(hipMemcpyAsync(d_times.p, times + k0, kn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            // outputs a failed solve does not reach stay NaN
+            HIP_TRY(hipMemsetAsync(dst, 0xff, (size_t)NS * kn * N * sizeof(double), c->stream));
         } else {
+            step.resize(kn);
+            w.resize((size_t)kn * 7);
             for (int64_t i = 0; i < kn; i++) {              // as locate_obs: tau in (t_n, t_{n+1}]
                 const double x = (times[k0 + i] - t0) / h;
                 int n = (int)std::ceil(x - 1e-9) - 1;
@@ -836,14 +851,32 @@ int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double*
             }
             HIP_TRY(hipMemcpyAsync(d_step.p, step.data(), kn * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync(d_w.p, w.data(), kn * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            if (!cpep) {                                    // state 1 at the outputs: the closed form of the launch tables
+                supp_output_rho(S, h, step, w, rho);
+                HIP_TRY(hipMemcpyAsync(d_rho.p, rho.data(), kn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            }
         }
-        cude::CpepArgs a = cpep_args(c);
-        a.obs = nullptr;                                    // no residuals: outputs only
-        a.cond = c->cond.p; a.nn = c->nn.p;
-        a.obs_step = d_step.p; a.obs_w = d_w.p; a.out_times = d_times.p;
-        a.T = (int32_t)kn;
-        a.traj = d_traj.p; a.partials = c->partials.p;
-        HIP_TRY(cude::launch_cpep(c->net, NS, false, a, c->stream));
+        if (cpep) {
+            cude::CpepArgs a = cpep_args(c);
+            a.obs = nullptr;                                // no residuals: outputs only
+            a.cond = c->cond.p; a.nn = c->nn.p;
+            a.obs_step = d_step.p; a.obs_w = d_w.p; a.out_times = d_times.p;
+            a.T = (int32_t)kn;
+            a.traj = d_traj.p; a.partials = c->partials.p;
+            HIP_TRY(cude::launch_cpep(c->net, NS, false, a, c->stream));
+        } else {
+            cude::SuppArgs a = supp_args(c);
+            a.ckpt_steps_only = 0;
+            a.cond = c->cond.p; a.nn = c->nn.p;
+            a.obs_step = d_step.p; a.obs_w = d_w.p; a.obs_rho = d_rho.p; a.out_times = d_times.p;
+            a.T = (int32_t)kn;
+            a.T_data = c->T;                                // outputs only: u0 = the data's first column
+            if (rows) { a.traj_ss = N; a.traj_st = 3 * N; a.traj_sn = 1; }
+            else { a.traj_ss = 1; a.traj_st = 3; a.traj_sn = 3 * kn; }
+            a.traj = dst; a.partials = c->partials.p;
+            HIP_TRY(cude::launch_supp(c->net, false, a, c->stream));
+            if (rows) HIP_TRY(cude::launch_supp_traj_transpose(N, (int)kn, d_rows.p, d_traj.p, c->stream));
+        }
         if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
         // device chunk [NS x kn x N] -> rows k0..k0+kn of the caller's [NS x n_times x N]
         HIP_TRY(hipMemcpy2DAsync(traj + (size_t)NS * k0, (size_t)NS * n_times * sizeof(double), d_traj.p,

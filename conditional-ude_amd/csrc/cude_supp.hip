@@ -23,14 +23,9 @@
 // It is still an INPUT of the network (value and first-layer weight gradient use it) and still part of the loss.
 #include "cude_device.h"
 #include "cude_kernels.h"
+#include "cude_supp.h"
 
 namespace cude {
-
-// HA / OA: activation functions other than tanh / softplus (cude_device.h CUDE_GENERAL_ACTS) select the general network
-template <int W, int D, int HA, int OA>
-struct SuppNetSel { using type = SuppNetG<W, D, HA, OA>; };
-template <int W, int D>
-struct SuppNetSel<W, D, kActHiddenTanh, kActOutSoftplus> { using type = SuppNet<W, D>; };
 
 template <int W, int D, int HA = kActHiddenTanh, int OA = kActOutSoftplus>
 struct SuppRhs {
@@ -484,8 +479,6 @@ static hipError_t launch_one(const SuppArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the shape of the reference's experiment with the other activation functions (stage-input mode only)
-#define CUDE_SUPP_GENERAL_SHAPES(X) X(3, 5) X(3, 3)
 template <int W, int D>
 static hipError_t launch_general(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
 #define Y(HA, OA)                                                                                 \
@@ -495,8 +488,6 @@ static hipError_t launch_general(const NetShape& net, bool grad, const SuppArgs&
 #undef Y
     return hipErrorInvalidValue;
 }
-
-#define CUDE_SUPP_SHAPES(X) X(3, 5) X(3, 2) X(4, 2) X(6, 2) X(5, 2) X(3, 3) X(8, 2) X(3, 4) X(4, 3) X(4, 4) X(5, 3) X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
 
 // resident waves per CU of the gradient kernel (stage-input mode; 0 = unknown): what the launch actually gets
 template <int W, int D>
@@ -535,6 +526,7 @@ hipError_t launch_supp(const NetShape& net, bool grad, const SuppArgs& a, hipStr
     if (net.generic()) return launch_supp_generic(net, grad, a, s);                 // fixed-step and adaptive alike
     if (net.nin != 4) return hipErrorInvalidValue;
     if (a.S == 0) return launch_supp_adaptive(net, grad, a, s);
+    if (a.T_data > 0) return grad ? hipErrorInvalidValue : launch_supp_dense(net, a, s);     // cude_supp_dense.hip
     if (net.general()) {
         if (a.ckpt_steps_only || a.act != nullptr) return hipErrorInvalidValue;
 #define X(W, D) if (net.width == W && net.depth == D) return launch_general<W, D>(net, grad, a, s);

@@ -920,10 +920,14 @@ def generate_data(group_means, group_sizes, timepoints, *, noise_additive=0.0, n
     return data, np.asarray(gt)
 
 
-def SuppressionProblem(network):
+def SuppressionProblem(network, tspan=(0.0, 30.0)):
     """Stand-in for `ODEProblem(ude_lsup!, [10,0,0], (0,30))` with the network closed over
-    (suppression/suppression.jl:18-20): carries the network shape; u0 comes from the data (:119)."""
-    return SimpleNamespace(network=network)
+    (suppression/suppression.jl:18-20): carries the network shape and the time span `simul` solves over when it saves
+    at times other than the data's; u0 comes from the data (:119)."""
+    t0, t1 = float(tspan[0]), float(tspan[1])
+    if not t1 > t0:
+        raise ValueError("SuppressionProblem: tspan must be increasing")
+    return SimpleNamespace(network=network, tspan=(t0, t1))
 
 
 def suppression_loss(p, args, *, n_steps=None):
@@ -943,10 +947,29 @@ def suppression_loss_and_gradient(p, args, *, n_steps=None):
 
 
 def simul(p, prob, individual_data, timepoints, *, n_steps=None):
-    """simul(p, prob, data, timepoints) -> 3 x T x N array (:107-115)."""
-    pop = _supp_population(prob, individual_data, timepoints, 0.0, n_steps)
+    """simul(p, prob, data, timepoints) -> 3 x len(timepoints) x N array (:107-115).  u0 = data[:, 0, :]; the solve runs
+    over the data's own times when there is one save time per data column, otherwise over prob.tspan with the states
+    saved at `timepoints` (dense output, as the reference's figure script calls it: figures.jl:66-74), which must lie
+    inside the span and be non-decreasing."""
+    data = np.asarray(individual_data, dtype=np.float64)
+    tp = np.asarray(timepoints, dtype=np.float64).reshape(-1)
+    if data.ndim != 3 or data.shape[0] != 3:
+        raise ValueError("individual_data must be (3, T, N)")
+    if tp.size == data.shape[1]:
+        pop = _supp_population(prob, individual_data, timepoints, 0.0, n_steps)
+        pop.engine.set_params(p.neural, p.theta)
+        return pop.engine.forward(want_traj=True)["traj"]
+    t0, t1 = getattr(prob, "tspan", (0.0, 30.0))
+    if tp.size == 0 or not (np.all(tp >= t0) and np.all(tp <= t1)):
+        raise ValueError(f"simul: save times must lie inside the problem's time span ({t0}, {t1})")
+    if np.any(np.diff(tp) < 0.0):
+        raise ValueError("simul: save times must be non-decreasing")
+    # a population over the span whose two columns are the initial state: the same span and step grid as the
+    # one-column-per-save-time path over those times
+    u0 = np.ascontiguousarray(data[:, :1, :])
+    pop = _supp_population(prob, np.concatenate([u0, u0], axis=1), np.array([t0, t1]), 0.0, n_steps)
     pop.engine.set_params(p.neural, p.theta)
-    return pop.engine.forward(want_traj=True)["traj"]
+    return pop.engine.simulate(tp)
 
 
 def fit_suppression_model(p_init, prob, data, timepoints, lam, *, select_best_n=1, adam_iters=2000, lbfgs_iters=2000,

@@ -244,7 +244,8 @@ class Engine:
 
     def simulate(self, times):
         """States of every subject at arbitrary non-decreasing times inside the population's time span (dense
-        output of the same fixed-step solve) -> array (n_state, len(times), N).  c-peptide models only."""
+        output of the same solve, fixed-step or adaptive) -> array (n_state, len(times), N).  Entries a subject's failed
+        adaptive solve does not reach are NaN."""
         t = _f64(times).reshape(-1)
         out = np.empty((self.N, t.size, self.n_state))
         check(self._lib.cude_simulate(self._h, t.size, _ptr(t), _ptr(out)))

@@ -794,7 +794,9 @@ end
 # ----------------------------------------------------------------------------------------------- suppression model
 struct SuppressionProblem          # stands in for ODEProblem(ude_lsup!, u0, tspan) with the network closed over
     network::Chain
+    tspan::Tuple{Float64,Float64}  # the span `simul` solves over when it saves at times other than the data's
 end
+SuppressionProblem(network::Chain) = SuppressionProblem(network, (0.0, 30.0))      # suppression.jl:20
 const SUPP_POPULATIONS = Dict{UInt64,Ctx}()
 function supp_population(prob::SuppressionProblem, data::AbstractArray{<:Real,3}, timepoints, λ; n_steps = nothing)
     n_steps = n_steps === nothing ? default_steps() : n_steps       # (fixed mode: DEFAULT_STEPS = 30)
@@ -820,11 +822,24 @@ function suppression_loss_and_gradient!(G, p, (prob, individual_data, timepoints
     G.neural .= gnn; G.theta .= gθ
     l
 end
-# simul(p, prob, individual_data, timepoints) -> 3 × T × N (:107-115)
+# simul(p, prob, individual_data, timepoints) -> 3 × length(timepoints) × N (:107-115): u0 = individual_data[:, 1, :]; over
+# the data's own times when there is one save time per data column, otherwise over prob.tspan with the states saved at
+# `timepoints` (dense output; figures.jl:66-74), which must lie inside the span and be non-decreasing
 function simul(p, prob::SuppressionProblem, individual_data, timepoints)
-    c = supp_population(prob, individual_data, timepoints, 0.0)
+    if length(timepoints) == size(individual_data, 2)
+        c = supp_population(prob, individual_data, timepoints, 0.0)
+        set_params!(c, p.neural, p.theta)
+        return forward(c; want_traj = true)[3]
+    end
+    t0, t1 = prob.tspan
+    tp = Vector{Float64}(timepoints)
+    (!isempty(tp) && all(t -> t0 <= t <= t1, tp)) ||
+        throw(ArgumentError("simul: save times must lie inside the problem's time span $(prob.tspan)"))
+    issorted(tp) || throw(ArgumentError("simul: save times must be non-decreasing"))
+    u0 = Array{Float64,3}(individual_data[:, 1:1, :])
+    c = supp_population(prob, cat(u0, u0; dims = 2), [t0, t1], 0.0)     # same span and step grid as the path above
     set_params!(c, p.neural, p.theta)
-    forward(c; want_traj = true)[3]
+    simulate_dense(c, tp)
 end
 # fit_suppression_model(p_init, prob, data, timepoints, λ; select_best_n) (:132-177): Adam() [η = 1e-3] × 2000, L-BFGS × 2000
 function fit_suppression_model(p_init, prob::SuppressionProblem, data, timepoints, λ; select_best_n = 1,

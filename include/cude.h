@@ -165,11 +165,18 @@ int32_t cude_get_params(cude_ctx* ctx, double* nn, double* cond);
 int32_t cude_forward(cude_ctx* ctx, double* loss, double* per_subject_sse, double* traj);
 
 /* Dense output: the states of every subject at n_times arbitrary, non-decreasing times inside [t[0], t[T-1]] (Tsit5
- * interpolant of the same fixed-step solve), at the context's current parameters.  Replaces
+ * interpolant of the same solve), at the context's current parameters (parameter set 0).  Replaces
  * `simulate(p_neural, p_individual, individual, network; timepoints = t0:0.1:tend)` (src/saem.jl:31-53, called with
  * dense grids at c-peptide/06-saem.jl:221-240) and `solve(model.problem, p=..., saveat=sol_timepoints)` of the
- * model-fit figures (c-peptide/02-conditional.jl, 03-symreg.jl:113).  traj receives [n_state x n_times x N]
- * column-major.  c-peptide models only (the reference simulates the suppression model at its data times: cude_forward). */
+ * model-fit figures (c-peptide/02-conditional.jl, 03-symreg.jl:113), and -- suppression model: u0 from the data's first
+ * column, n_state = 3 -- `simul(p, prob, individual_data, timepoints)` at save times other than the data's
+ * (suppression/src/suppression_model.jl:107-115, as suppression/figures.jl:66-74 calls it on range(0, 30, length = 100)).
+ * Fixed-step or adaptive as the context is: the adaptive solve takes the same steps as cude_forward's (the output times are
+ * `saveat`, not `tstops`).  traj receives [n_state x n_times x N] column-major.  A failed subject leaves the others
+ * unaffected: an adaptive solve that fails (non-finite error estimate, step limit) leaves NaN at every output time it
+ * did not reach, both models; a suppression subject with a non-finite input (theta, u0, a network parameter) gets NaN
+ * at every output time (as the oracle's adaptive solve reports it); c-peptide values are otherwise what the
+ * arithmetic gives, as before. */
 int32_t cude_simulate(cude_ctx* ctx, int32_t n_times, const double* times, double* traj);
 
 /* Multi-start screening: forward-only loss of n_sets candidate parameter sets over the resident
@@ -438,9 +445,12 @@ int32_t cude_xchg_info(cude_ctx* ctx, int32_t* n_ranks, int32_t* rank, int32_t* 
  * "2:L" | "3:B:L"), "cpep_keep", "supp_store", "supp_ckpt", "tape_steps", "exp_table", "ms_split", "auto_regroup",
  * "poll_pinned", "debug_selector", "xchg_allow_plain", "xchg_fail_kinds" (tests), "force_fallback" (tests: cude_set_network takes the fallback kernel for tuned shapes too), "adaptive_team" (adaptive mode, small c-peptide
  * populations: a step's five network evaluations on five waves; 0 = the one-wave kernels), "fit_spec" (cude_fit_conditional: probes per forward launch, 0 = one, 1 ... 4 = golden-section steps per launch, -1 = by size), "mh_spec" (speculative Metropolis steps per
- * launch pair in cude_mh_estep / cude_mh_chain: 0 off, 2 ... 4, -1 = by population size; the chain is the same bit for bit).  Values are decimal integers as text unless noted.  Every option is also read once
+ * launch pair in cude_mh_estep / cude_mh_chain: 0 off, 2 ... 4, -1 = by population size; the chain is the same bit for bit),
+ * "dense_chunk" (cude_simulate: output times per launch, 0 = ~1 GB of scratch; tests force several launches with it),
+ * "dense_layout" (cude_simulate, suppression model: 0 = the caller's layout written directly, the default; 1 =
+ * lane-contiguous rows + a transpose kernel).  Values are decimal integers as text unless noted.  Every option is also read once
  * at cude_create from its environment variable (CUDE_CPEP_PATH, CUDE_CPEP_KEEP, CUDE_SUPP_STORE, CUDE_SUPP_CKPT,
- * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM).
+ * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT).
  * Options that shape the launch path take effect at the next cude_set_population_*.  No reference line: these are
  * properties of this implementation. */
 int32_t cude_set_option(cude_ctx* ctx, const char* name, const char* value);
