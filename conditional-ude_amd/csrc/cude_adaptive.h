@@ -234,6 +234,149 @@ struct SuppAdOut : SuppAd<W, D, HA, OA> {
     }
 };
 
+// ---------------------------------------------------------------------------------- tangent policies (cude_sensitivity)
+// The same solves carrying d u / d(conditional) next to u: the state vector of the one-body kernel is [u; du], the
+// right-hand side of the second half is the tangent-linear one (Net::eval_jvp), and the step-size control reads the first
+// NERR states only -- so the accepted steps are those of the plain solve (cude_forward) and the tangent is the derivative
+// of the accepted-step map, the convention of the adaptive adjoint.  (OrdinaryDiffEq's norm under ForwardDiff duals also
+// weighs the partials; that variant is not built: INTEGRATION.md.)  The primal operations are those of CpepAd / SuppAd in
+// the same order.  A policy with a member NERR is a tangent policy to the kernel:
+//   rhs(st, te, Y, du)               the whole right-hand side (st: the kernel's phase, -2 = k_1 of the first step)
+//   record(a, slot, n, t, dt, y)     accepted step n, written in the layout of the gradient's tape (cude_adaptive_steps)
+//   finish(a, i, active, bad)        per-subject outputs behind the solve
+template <class M, class = void>
+struct AdTangent {
+    static constexpr bool value = false;
+    static constexpr int nerr = M::NS;
+};
+template <class M>
+struct AdTangent<M, decltype((void)M::NERR)> {
+    static constexpr bool value = true;
+    static constexpr int nerr = M::NERR;
+};
+
+template <class Net>
+struct CpepAdTan : CpepAd<Net> {
+    using Base = CpepAd<Net>;
+    static constexpr int NS = 4, NERR = 2;          // [u1, u2, du1, du2]
+    using Args = CpepSensArgs;
+    double dc[Net::NCST];
+    double dbase, prod_last, dprod_last, info, score;
+    __device__ __forceinline__ double init(const Args& a, double* s_extra, int lane_, int64_t i, int64_t set, double (&y)[NS]) {
+        double y2[2];
+        const double chk = Base::init(a, s_extra, lane_, i, set, y2);
+        y[0] = y2[0]; y[1] = y2[1]; y[2] = 0.0; y[3] = 0.0;
+        Net::cond_tangent(this->p, this->cst0, dc);
+        dbase = prod_last = dprod_last = info = score = 0.0;
+        return chk;
+    }
+    __device__ __forceinline__ void rhs(int st, double te, const double (&Y)[NS], double (&du)[NS]) {
+        // the forcing depends on time only and c_6 = c_7 = 1: stage 7 (st == 6, wave-uniform) reuses stage 6's value;
+        // st == -2: the baseline NN([0; e^beta]) first (one call site for both)
+        if (st != 6) {
+            const int nr = st == -2 ? 2 : 1;
+#pragma unroll 1
+            for (int r = 0; r < nr; r++) {
+                const bool is_base = st == -2 && r == 0;
+                const double xx[1] = {is_base ? 0.0 : this->forcing_input(te)}, dx[1] = {0.0};
+                double dv;
+                const double v = Net::template eval_jvp<false>(this->p, this->c, xx, dc, dx, &dv);
+                if (is_base) { this->base = v; dbase = dv; }
+                else { prod_last = v; dprod_last = dv; }
+            }
+        }
+        du[0] = fma(this->a11, Y[0], fma(this->a12, Y[1], this->f0 + (prod_last - this->base)));
+        du[1] = fma(this->a21, Y[0], this->a22 * Y[1]);
+        du[2] = fma(this->a11, Y[2], fma(this->a12, Y[3], dprod_last - dbase));
+        du[3] = fma(this->a21, Y[2], this->a22 * Y[3]);
+    }
+    __device__ __forceinline__ double residual2(const Args& a, int oi, int64_t i, const double (&o)[NS], bool active) {
+        if (a.out.sens != nullptr && active) {
+            double* tr = a.out.sens + (int64_t)2 * (oi + (int64_t)a.T * i);
+            tr[0] = o[2];
+            tr[1] = o[3];
+        }
+        const double r = o[0] - a.obs[(int64_t)oi * a.N + i];
+        info = fma(o[2], o[2], info);
+        score = fma(r, o[2], score);
+        return r * r;
+    }
+    __device__ __forceinline__ void record(const Args& a, int64_t slot, int n, double, double dt, const double (&)[NS]) const {
+        if (a.tape != nullptr && n < a.tape_cap) a.tape[(int64_t)n * a.N + slot] = dt;
+    }
+    __device__ __forceinline__ void finish(const Args& a, int64_t i, bool active, bool bad) const {
+        if (!active) return;
+        const double nan = __builtin_nan("");
+        if (a.out.info != nullptr) a.out.info[i] = bad ? nan : info;
+        if (a.out.score != nullptr) a.out.score[i] = bad ? nan : score;
+        if (bad && a.out.sens != nullptr)
+            for (int q = 0; q < 2 * a.T; q++) a.out.sens[(int64_t)2 * a.T * i + q] = nan;
+    }
+};
+
+template <int W, int D, int HA = kActHiddenTanh, int OA = kActOutSoftplus>
+struct SuppAdTan : SuppAd<W, D, HA, OA> {
+    using Base = SuppAd<W, D, HA, OA>;
+    using typename Base::Net;
+    static constexpr int NS = 5, NERR = 3;          // [u1, u2, u3, du2, du3]: state 1 depends on no parameter
+    using Args = SuppSensArgs;
+    double dc[W];
+    double info, score;
+    __device__ __forceinline__ double init(const Args& a, double*, int, int64_t i, int64_t set, double (&y)[NS]) {
+        double y3[3];
+        const double chk = Base::init(a, nullptr, 0, i, set, y3);
+        y[0] = y3[0]; y[1] = y3[1]; y[2] = y3[2]; y[3] = 0.0; y[4] = 0.0;
+        Net::cond_tangent(this->p, exp(a.cond[set * a.set_stride_cond + i]), dc);
+        info = score = 0.0;
+        return chk;
+    }
+    __device__ __forceinline__ void rhs(int, double, const double (&Y)[NS], double (&du)[NS]) const {
+        const double x[3] = {Y[0], Y[1], Y[2]}, dx[3] = {0.0, Y[3], Y[4]};
+        double duh;
+        const double uh = Net::template eval_jvp<true>(this->p, this->c, x, dc, dx, &duh);
+        du[0] = -0.4 * Y[0];
+        du[1] = fma(0.4, Y[0], -uh);
+        du[2] = fma(-0.3, Y[2], uh);
+        du[3] = -duh;
+        du[4] = fma(-0.3, Y[4], duh);
+    }
+    __device__ __forceinline__ double residual2(const Args& a, int oi, int64_t i, const double (&o)[NS], bool active) {
+        if (a.out.sens != nullptr && active) {
+            double* tr = a.out.sens + (int64_t)3 * (oi + (int64_t)a.T * i);
+            tr[0] = 0.0;
+            tr[1] = o[3];
+            tr[2] = o[4];
+        }
+        double s2 = 0.0;
+#pragma unroll
+        for (int s = 0; s < 3; s++) {
+            const double r = o[s] - a.data[((int64_t)s * a.T + oi) * a.N + i];
+            s2 = fma(r * a.iscale2[s], r, s2);
+            if (s > 0) {
+                info = fma(o[2 + s] * a.iscale2[s], o[2 + s], info);
+                score = fma(r * a.iscale2[s], o[2 + s], score);
+            }
+        }
+        return s2;
+    }
+    __device__ __forceinline__ void record(const Args& a, int64_t slot, int n, double t, double dt, const double (&y)[NS]) const {
+        if (a.tape == nullptr || n >= a.tape_cap) return;
+        double* e = a.tape + (int64_t)n * kSuppTapeRows * a.N + slot;
+        e[0] = t;
+        e[a.N] = dt;
+#pragma unroll
+        for (int s = 0; s < 3; s++) e[(2 + s) * a.N] = y[s];
+    }
+    __device__ __forceinline__ void finish(const Args& a, int64_t i, bool active, bool bad) const {
+        if (!active) return;
+        const double nan = __builtin_nan("");
+        if (a.out.info != nullptr) a.out.info[i] = bad ? nan : info;
+        if (a.out.score != nullptr) a.out.score[i] = bad ? nan : score;
+        if (bad && a.out.sens != nullptr)
+            for (int q = 0; q < 3 * a.T; q++) a.out.sens[(int64_t)3 * a.T * i + q] = nan;
+    }
+};
+
 __device__ __forceinline__ double rms(const double* v, int n) {
     double s = 0.0;
     for (int k = 0; k < n; k++) s = fma(v[k], v[k], s);

@@ -151,6 +151,7 @@ struct cude_ctx {
     double abstol = 1e-6, reltol = 1e-3;   // adaptive mode (n_steps == 0): OrdinaryDiffEq's defaults
     // parameters / gradients / optimiser
     cude::api::DevBuf<double> nn, cond, g_nn, g_cond, sse, auc, partials, traj;
+    cude::api::DevBuf<double> sens, sens_info, sens_score;     // cude_sensitivity: [n_state x T x N], [N], [N] (first call)
     // chunked gradient path (cude_cpep2.hip)
     int chunks = 1;
     int n_cu = 256;         // compute units of the device (setup_chunks)

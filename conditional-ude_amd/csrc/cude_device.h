@@ -913,6 +913,85 @@ struct Mlp {
         }
         *dcond = s;
     }
+
+    // ---- forward mode (tangent-linear evaluation; cude_sens.hip and the tangent policies of cude_adaptive.h).
+    // d c_j / d(conditional as stored): the conditional parameter is constant input NV and enters as cst0 = exp(value),
+    // so the first-layer offsets move by W1[j, NV] * cst0 per unit of it
+    __device__ static __forceinline__ void cond_tangent(cptr_t p, double cst0, double (&dc)[W]) {
+#pragma unroll
+        for (int j = 0; j < W; j++) dc[j] = p[j + W * NV] * cst0;
+    }
+    // Value and directional derivative in one sweep.  The direction is (dx, dc): a tangent of the variable inputs
+    // (HAS_DX; otherwise they do not move) and of the first-layer offsets.  Every weight column is fetched once and feeds
+    // the primal and the tangent multiply-add; the primal operations are those of `eval`, in the same order, so the value
+    // returned is `eval`'s bit for bit.  *dy receives d(out).
+    template <bool HAS_DX>
+    __device__ static __forceinline__ double eval_jvp(cptr_t p, const double (&c)[W], const double (&x)[NV],
+                                                      const double (&dc)[W], const double (&dx)[NV], double* dy) {
+        p = launder(p);
+        double z[W], dz[W], h[W], dh[W];
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            const SCol<W> col = ld_col<W>(p, W * i);
+#pragma unroll
+            for (int j = 0; j < W; j++) {
+                z[j] = fma(col.v[j], x[i], i == 0 ? c[j] : z[j]);
+                if (HAS_DX) dz[j] = fma(col.v[j], dx[i], i == 0 ? dc[j] : dz[j]);
+            }
+        }
+        if (!HAS_DX) {
+#pragma unroll
+            for (int j = 0; j < W; j++) dz[j] = dc[j];
+        }
+        act_hidden_vec<W, HA, TT>(z, h);
+#pragma unroll
+        for (int j = 0; j < W; j++) dh[j] = act_hidden_deriv<HA>(h[j]) * dz[j];
+#pragma unroll
+        for (int l = 1; l < D; l++) {
+            const int o = L1 + (l - 1) * LH;
+            CUDE_FENCE();
+            if constexpr (LDS_BIAS) {
+#pragma unroll
+                for (int j = 0; j < W; j++) z[j] = s_bias[(l - 1) * W + j];
+            } else {
+                const SCol<W> b = ld_col<W>(p, o + W * W);
+#pragma unroll
+                for (int j = 0; j < W; j++) z[j] = seed_from_sgpr(b.v[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < W; j++) dz[j] = 0.0;
+#pragma unroll
+            for (int i0 = 0; i0 < W; i0 += CG) {
+                CUDE_FENCE();
+                constexpr int kG = CG;
+                const SCol<W * kG> col = ld_col<W * kG>(p, o + W * i0);
+#pragma unroll
+                for (int g = 0; g < kG; g++)
+#pragma unroll
+                    for (int j = 0; j < W; j++)
+                        if (i0 + g < W) {
+                            z[j] = fma(col.v[g * W + j], h[i0 + g], z[j]);
+                            dz[j] = fma(col.v[g * W + j], dh[i0 + g], dz[j]);
+                        }
+            }
+            CUDE_FENCE();
+            act_hidden_vec<W, HA, TT>(z, h);
+#pragma unroll
+            for (int j = 0; j < W; j++) dh[j] = act_hidden_deriv<HA>(h[j]) * dz[j];
+        }
+        CUDE_FENCE();
+        const SCol<W> wo = ld_col<W>(p, OUT);
+        double z0 = seed_from_sgpr(p[OUT + W]), z1 = 0.0, d0 = 0.0, d1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            if (i & 1) { z1 = fma(wo.v[i], h[i], z1); d1 = fma(wo.v[i], dh[i], d1); }
+            else { z0 = fma(wo.v[i], h[i], z0); d0 = fma(wo.v[i], dh[i], d0); }
+        }
+        double sig;
+        const double y = act_out<OA, TT>(z0 + z1, &sig);
+        *dy = sig * (d0 + d1);
+        return y;
+    }
 };
 
 // the networks of the fixed-step kernel families with their tanh form (see act_tanh_vec)
@@ -1008,6 +1087,20 @@ struct MmProd {
     template <class A>
     __device__ static __forceinline__ double grad_cond(cptr_t, const A& acc, const double (&cst)[1]) {
         return RAW ? acc[1] : acc[1] * cst[0];
+    }
+    // ---- forward mode, as Mlp: d k / d(conditional as stored), and the value with its directional derivative
+    __device__ static __forceinline__ void cond_tangent(cptr_t, double cst0, double (&dc)[1]) { dc[0] = RAW ? 1.0 : cst0; }
+    template <bool HAS_DX>
+    __device__ static __forceinline__ double eval_jvp(cptr_t p, const double (&c)[1], const double (&x)[1],
+                                                      const double (&dc)[1], const double (&dx)[1], double* dy) {
+        const double p0 = p[0];
+        const double v = (p0 * x[0]) / (x[0] + c[0]);
+        const double r = 1.0 / (x[0] + c[0]);
+        double d = -(p0 * x[0]) * r * r * dc[0];             // d/dk
+        if (HAS_DX) d = fma(p0 * c[0] * r * r, dx[0], d);    // d/dx
+        const bool pos = x[0] >= 0.0;
+        *dy = pos ? d : 0.0;
+        return pos ? v : 0.0;
     }
 };
 

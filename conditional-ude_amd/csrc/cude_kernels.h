@@ -260,6 +260,24 @@ struct SuppArgs {
     int64_t traj_ss, traj_st, traj_sn;
 };
 
+// Forward-mode (tangent-linear) solves, cude_sensitivity (cude_sens.hip): the population and solver fields of the model's
+// own argument block, and the three per-subject outputs of the tangent (any of them nullptr = not wanted).  Blocks of their
+// own, so that the argument blocks of every other kernel stay what they are.  One parameter set, one lane per subject.
+struct SensOut {
+    double* sens = nullptr;  // [n_state x T x N] column-major: d u_s(t_j) / d cond_i
+    double* info = nullptr;  // [N] sum over the observed outputs of (w * d yhat / d cond)^2
+    double* score = nullptr; // [N] sum of w^2 (yhat - y) d yhat / d cond
+};
+struct CpepSensArgs : CpepArgs {
+    SensOut out;
+};
+struct SuppSensArgs : SuppArgs {
+    SensOut out;
+};
+// hipErrorInvalidValue when no tuned kernel is compiled for the shape (the fallback kernel has no tangent)
+hipError_t launch_cpep_sens(const NetShape& net, int n_state, const CpepSensArgs& a, hipStream_t s);
+hipError_t launch_supp_sens(const NetShape& net, const SuppSensArgs& a, hipStream_t s);
+
 // the fallback kernel for networks no tuned kernel is compiled for (net.generic(); cude_generic.hip)
 hipError_t launch_cpep_generic(const NetShape& net, int n_state, bool grad, const CpepArgs& a, hipStream_t s);
 hipError_t launch_supp_generic(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s);

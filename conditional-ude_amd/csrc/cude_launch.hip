@@ -887,6 +887,70 @@ int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double*
     return CUDE_OK;
 }
 
+int32_t cude_sensitivity(cude_ctx* c, double* sens, double* info, double* score, double* sse) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn || !c->have_cond) return fail(CUDE_ERR_STATE, "parameters not set");
+    if (c->net.generic())
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_sensitivity: the network of this context runs on the fallback kernel "
+                                          "(cude_set_network), which has no tangent-linear solve");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_sensitivity under stream capture");
+    const bool cpep = is_cpep(c);
+    const int NS = cpep ? c->cfg.n_state : 3;
+    const int64_t N = c->N;
+    if (sens) HIP_TRY(c->sens.reserve((size_t)NS * c->T * N));
+    HIP_TRY(c->sens_info.reserve((size_t)N));
+    HIP_TRY(c->sens_score.reserve((size_t)N));
+    // adaptive mode: the accepted steps go to the gradient's tape, so that cude_adaptive_steps reports them
+    if (adaptive(c) && (rc = ensure_tape(c))) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->timing && (c->timing_count++ % c->timing_period) == 0) {
+        if (c->ev_used == c->ev_pool.size()) {
+            hipEvent_t a, b;
+            HIP_TRY(hipEventCreate(&a));
+            HIP_TRY(hipEventCreate(&b));
+            c->ev_pool.emplace_back(a, b);
+        }
+        e0 = c->ev_pool[c->ev_used].first;
+        e1 = c->ev_pool[c->ev_used].second;
+        c->ev_used++;
+        HIP_TRY(hipEventRecord(e0, c->stream));
+    }
+    cude::SensOut out;
+    out.sens = sens ? c->sens.p : nullptr;
+    out.info = c->sens_info.p;
+    out.score = c->sens_score.p;
+    hipError_t le;
+    if (cpep) {
+        cude::CpepSensArgs a{};
+        static_cast<cude::CpepArgs&>(a) = cpep_args(c);
+        a.cond = c->cond.p; a.nn = c->nn.p; a.sse = c->sse.p; a.partials = c->partials.p;
+        a.out = out;
+        le = cude::launch_cpep_sens(c->net, c->cfg.n_state, a, c->stream);
+    } else {
+        cude::SuppSensArgs a{};
+        static_cast<cude::SuppArgs&>(a) = supp_args(c);
+        a.cond = c->cond.p; a.nn = c->nn.p; a.sse = c->sse.p; a.partials = c->partials.p;
+        a.out = out;
+        le = cude::launch_supp_sens(c->net, a, c->stream);
+    }
+    if (le == hipErrorInvalidValue) return fail(CUDE_ERR_UNSUPPORTED, "cude_sensitivity: no tangent kernel compiled for this network shape / model");
+    HIP_TRY(le);
+    if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
+    if (adaptive(c)) { c->have_counts = true; c->have_tape = true; }
+    // [sum SSE, n_failed] behind the launch, as a forward evaluation's (finish_loss sets cude_n_failed)
+    c->loss_in_pinned = false;
+    c->tail_in_pinned = false;
+    HIP_TRY(cude::launch_reduce_cols(c->partials.p, c->nblocks, c->P + 2, c->P, 2, c->g_nn.p, c->stream));
+    if (sens)
+        HIP_TRY(hipMemcpyAsync(sens, c->sens.p, (size_t)NS * c->T * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (info) HIP_TRY(hipMemcpyAsync(info, c->sens_info.p, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (score) HIP_TRY(hipMemcpyAsync(score, c->sens_score.p, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (sse) HIP_TRY(hipMemcpyAsync(sse, c->sse.p, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return finish_loss(c, nullptr, nullptr);
+}
+
 int32_t cude_n_failed(cude_ctx* c, int64_t* n_failed) {
     if (!c || !n_failed) return fail(CUDE_ERR_ARG, "null argument");
     *n_failed = c->last_failed;

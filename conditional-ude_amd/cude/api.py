@@ -34,6 +34,7 @@ Fminbox(LBFGS).
 import hashlib
 import math
 from collections import OrderedDict
+from statistics import NormalDist
 from types import SimpleNamespace
 
 import numpy as np
@@ -852,6 +853,64 @@ def likelihood_profiles(betas, neural_network_parameters, models, timepoints, cp
     return nll, nll_min, values
 
 
+# ----------------------------------------------------------------------------- sensitivities, Fisher information
+def sensitivities(theta, args, *, n_steps=None):
+    """Output sensitivities of every subject to its own conditional parameter, by the library's tangent-linear solve
+    (cude_sensitivity) -- the partials the reference's solves carry under ForwardDiff (src/parameter-estimation.jl:59,165).
+    args = (models, timepoints, cpeptide_data), theta.neural / theta.conditional as `loss`.  Returns
+    (sens (n_state, T, N) = d u_s(t_j) / d beta_i, info (N,) = sum_j (d yhat_j / d beta_i)^2, score (N,) = half the
+    derivative of SSE_i, sse (N,)).  The derivative is with respect to the parameter as stored (log-space beta; k itself
+    for a list of CPeptideODEModel).  Failed subjects are NaN."""
+    models, timepoints, data = args
+    if _is_model(models):
+        models, data = [models], np.asarray(data)[None, :]
+    if isinstance(models[0], CPeptideODEModel):
+        pop = _population(models, timepoints, data, n_steps, cond_space="raw")
+        nn = getattr(theta, "neural", None)
+        cond = getattr(theta, "conditional", getattr(theta, "ode", theta))
+        pop.engine.set_params(pop.shared if nn is None else nn, np.asarray(cond, dtype=np.float64).reshape(-1)[:pop.N])
+    else:
+        pop = _population(models, timepoints, data, n_steps)
+        pop.engine.set_params(theta.neural, np.asarray(theta.conditional, dtype=np.float64).reshape(-1)[:pop.N])
+    out = pop.engine.sensitivity()
+    return out["sens"], out["info"], out["score"], out["sse"]
+
+
+def conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data, *, sigma=None,
+                                n_steps=None):
+    """Asymptotic standard error of every subject's conditional parameter: sigma / sqrt(info_i), the inverse square root
+    of the Fisher information info_i / sigma^2 of a Gaussian error model.  sigma = None: the per-subject maximum-likelihood
+    value sigma_i^2 = SSE_i / n_i, the closed form loss_sigma (src/parameter-estimation.jl:70-75) is minimised by.  A
+    subject whose data do not identify the parameter (info = 0) gets inf."""
+    theta = ComponentArray(neural=neural_network_parameters, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
+    _, info, _, sse = sensitivities(theta, (models, timepoints, cpeptide_data), n_steps=n_steps)
+    return _standard_errors(info, sse, len(timepoints), sigma)
+
+
+def _standard_errors(info, sse, n_obs, sigma):
+    info, sse = np.asarray(info, dtype=np.float64), np.asarray(sse, dtype=np.float64)
+    sig = np.sqrt(sse / n_obs) if sigma is None else np.broadcast_to(np.asarray(sigma, dtype=np.float64), info.shape)
+    se = np.full(info.shape, np.inf)
+    ok = info > 0.0
+    se[ok] = sig[ok] / np.sqrt(info[ok])
+    se[np.isnan(info)] = np.nan
+    return se
+
+
+def _wald(betas, se, level):
+    z = NormalDist().inv_cdf(0.5 + level / 2)
+    return [(float(b - z * s), float(b + z * s)) for b, s in zip(np.asarray(betas, dtype=np.float64).reshape(-1), se)]
+
+
+def wald_confidence_intervals(betas, neural_network_parameters, models, timepoints, cpeptide_data, *, sigma=None,
+                              level=0.95, n_steps=None):
+    """Wald intervals beta_i -/+ z_level * se_i, one (lower, upper) pair per subject as find_confidence_intervals returns
+    for a profile; (-inf, inf) where the data do not identify the parameter."""
+    se = conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data, sigma=sigma,
+                                     n_steps=n_steps)
+    return _wald(betas, se, level)
+
+
 # ----------------------------------------------------------------------------- suppression model
 class _SuppPop:
     def __init__(self, data, timepoints, net, lam, n_steps, device):
@@ -936,6 +995,16 @@ def suppression_loss(p, args, *, n_steps=None):
     pop = _supp_population(prob, data, timepoints, lam, n_steps)
     pop.engine.set_params(p.neural, p.theta)
     return pop.engine.forward()["loss"]
+
+
+def suppression_sensitivities(p, args, *, n_steps=None):
+    """sensitivities for the suppression model: args = (prob, individual_data, timepoints, lambda) as suppression_loss.
+    Returns (sens (3, T, N) = d u / d theta_i, info, score, sse) with the loss's weights 1 / scale_s."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, p.theta)
+    out = pop.engine.sensitivity()
+    return out["sens"], out["info"], out["score"], out["sse"]
 
 
 def suppression_loss_and_gradient(p, args, *, n_steps=None):

@@ -251,6 +251,14 @@ class Engine:
         check(self._lib.cude_simulate(self._h, t.size, _ptr(t), _ptr(out)))
         return np.ascontiguousarray(out.transpose(2, 1, 0))
 
+    def sensitivity(self, want_sens=True):
+        """cude_sensitivity at the context's parameters: dict(sens (n_state, T, N) = d u / d cond_i (None unless
+        want_sens), info (N,), score (N,), sse (N,)); failed subjects are NaN."""
+        sens = np.empty((self.N, self.T, self.n_state)) if want_sens else None
+        info, score, sse = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        check(self._lib.cude_sensitivity(self._h, _ptr(sens), _ptr(info), _ptr(score), _ptr(sse)))
+        return {"sens": None if sens is None else sens.transpose(2, 1, 0), "info": info, "score": score, "sse": sse}
+
     def multistart_forward(self, nn_sets, cond_sets):
         """Losses of K candidate (network, conditional) parameter sets in one launch.
         nn_sets: (K, P); cond_sets: (K, N)."""

@@ -26,7 +26,8 @@ using Statistics: mean, var
 export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEModel, CPeptideConditionalCovariateUDEModel,
        CPeptideUDEModel,
        loss, loss_sigma, loss_and_gradient!, train, train_with_sigma, evaluate_model, likelihood_profile,
-       SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM
+       SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
+       sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals
 
 const LIB = get(ENV, "CUDE_HIP_LIB", "libcude_hip.so")
 const MODEL_CPEP, MODEL_SUPP, MODEL_CPEP_SYM = Int32(0), Int32(1), Int32(2)
@@ -129,6 +130,17 @@ function n_failed(c::Ctx)
     n = Ref{Int64}(0)
     check(ccall((:cude_n_failed, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), c.h, n))
     Int(n[])
+end
+
+# output sensitivities to every subject's own conditional parameter (tangent-linear solve): sens [n_state × T × N],
+# info, score, sse [N]; failed subjects are NaN
+function sensitivity(c::Ctx; want_sens = true)
+    sens = want_sens ? Array{Float64,3}(undef, c.n_state, c.T, c.N) : nothing
+    info = Vector{Float64}(undef, c.N); score = Vector{Float64}(undef, c.N); sse = Vector{Float64}(undef, c.N)
+    GC.@preserve sens info score sse check(ccall((:cude_sensitivity, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, sens === nothing ? C_NULL : pointer(sens), info, score, sse))
+    sens, info, score, sse
 end
 
 # states of every subject at arbitrary times inside the time span: [n_state × n_times × N]
@@ -791,6 +803,54 @@ function likelihood_profile(β, neural_network_parameters, model::CPeptideCondit
     nll_values, nll_minimum, parameter_values
 end
 
+# ----------------------------------------------------------------------------------------------- sensitivities
+# sensitivities(θ, (models, timepoints, cpeptide_data)) -> (sens [n_state × T × N], info, score, sse): the partials
+# ∂u/∂βᵢ the reference's solves carry under ForwardDiff (src/parameter-estimation.jl:59,165), by cude_sensitivity
+function sensitivities(θ, (models, timepoints, cpeptide_data); n_steps = nothing)
+    c = population(models, timepoints, cpeptide_data; n_steps = n_steps)
+    set_params!(c, θ.neural, θ.conditional)
+    sensitivity(c)
+end
+function standard_errors(info, sse, n_obs, sigma)
+    [isnan(info[i]) ? NaN : info[i] > 0 ? (sigma === nothing ? sqrt(sse[i] / n_obs) : sigma) / sqrt(info[i]) : Inf
+     for i in eachindex(info)]
+end
+# σ / √infoᵢ; sigma = nothing: σᵢ² = SSEᵢ / nᵢ (the closed form loss_sigma is minimised by); info = 0 -> Inf
+function conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data;
+                                     sigma = nothing, n_steps = nothing)
+    _, info, _, sse = sensitivities((neural = neural_network_parameters, conditional = betas),
+                                    (models, timepoints, cpeptide_data); n_steps = n_steps)
+    standard_errors(info, sse, length(timepoints), sigma)
+end
+# standard normal quantile (Acklam's rational approximation, relative error 1.2e-9; no Distributions dependency)
+function normal_quantile(p)
+    a = (-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02,
+         -3.066479806614716e+01, 2.506628277459239e+00)
+    b = (-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01,
+         -1.328068155288572e+01)
+    cc = (-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00,
+          4.374664141464968e+00, 2.938163982698783e+00)
+    d = (7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00)
+    if p < 0.02425
+        q = sqrt(-2 * log(p))
+        return (((((cc[1] * q + cc[2]) * q + cc[3]) * q + cc[4]) * q + cc[5]) * q + cc[6]) /
+               ((((d[1] * q + d[2]) * q + d[3]) * q + d[4]) * q + 1)
+    elseif p > 1 - 0.02425
+        return -normal_quantile(1 - p)
+    end
+    q = p - 0.5; r = q * q
+    (((((a[1] * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * r + a[6]) * q /
+        (((((b[1] * r + b[2]) * r + b[3]) * r + b[4]) * r + b[5]) * r + 1)
+end
+# Wald intervals βᵢ ∓ z·seᵢ, one (lower, upper) pair per subject as find_confidence_intervals returns for a profile
+function wald_confidence_intervals(betas, neural_network_parameters, models, timepoints, cpeptide_data;
+                                   sigma = nothing, level = 0.95, n_steps = nothing)
+    se = conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data;
+                                     sigma = sigma, n_steps = n_steps)
+    z = normal_quantile(0.5 + level / 2)
+    [(betas[i] - z * se[i], betas[i] + z * se[i]) for i in eachindex(se)]
+end
+
 # ----------------------------------------------------------------------------------------------- suppression model
 struct SuppressionProblem          # stands in for ODEProblem(ude_lsup!, u0, tspan) with the network closed over
     network::Chain
@@ -814,6 +874,12 @@ function suppression_loss(p, (prob, individual_data, timepoints, λ))
     c = supp_population(prob, individual_data, timepoints, λ)
     set_params!(c, p.neural, p.theta)
     forward(c)[1]
+end
+# (sens [3 × T × N] = ∂u/∂θᵢ, info, score, sse) with the loss's weights 1/scaleₛ
+function suppression_sensitivities(p, (prob, individual_data, timepoints, λ); n_steps = nothing)
+    c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
+    set_params!(c, p.neural, p.theta)
+    sensitivity(c)
 end
 function suppression_loss_and_gradient!(G, p, (prob, individual_data, timepoints, λ))
     c = supp_population(prob, individual_data, timepoints, λ)

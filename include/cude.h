@@ -179,6 +179,28 @@ int32_t cude_forward(cude_ctx* ctx, double* loss, double* per_subject_sse, doubl
  * arithmetic gives, as before. */
 int32_t cude_simulate(cude_ctx* ctx, int32_t n_times, const double* times, double* traj);
 
+/* Per-subject output sensitivities: the derivative of every subject's trajectory with respect to its OWN conditional
+ * parameter, by a tangent-linear (forward-mode) solve next to the solve itself -- what every solve of the reference carries
+ * under ForwardDiff (sensealg = ForwardDiffSensitivity(), src/parameter-estimation.jl:59; AutoForwardDiff() through
+ * `solve`, src/parameter-estimation.jl:165,370 and suppression/src/suppression_model.jl:155), restricted to the direction
+ * d/d(conditional_i).  All four outputs are optional; the context's current parameters are used.
+ *   sens  [n_state x T x N] column-major (cude_forward's traj layout): d u_s(t_j) / d cond_i at the data's time points;
+ *         column t_0 is exactly 0 (u0 depends on no parameter)
+ *   info  [N]  sum over the observed outputs of (w * d yhat / d cond)^2 in the loss's own weighting -- c-peptide models:
+ *         state 1, w = 1; suppression model: all three states, w = 1 / scale_s.  The Fisher information of cond_i is
+ *         info / sigma^2; an unidentifiable subject (constant glucose) has info = 0
+ *   score [N]  sum of w^2 (yhat - y) d yhat / d cond = (1/2) d SSE_i / d cond_i; against cude_loss_grad:
+ *         g_cond_i = 2 * score_i / n_global
+ *   sse   [N]  cude_forward's per_subject_sse
+ * The derivative is with respect to the parameter AS STORED: log-space beta / theta (the chain factor exp(beta) is
+ * included), or k itself where cude_config.cond_space is CUDE_COND_RAW.  Adaptive mode: step control reads the solve's
+ * own error estimate only, so the accepted steps are cude_forward's and the result is the derivative of the
+ * accepted-step map -- the adaptive gradient's convention (OrdinaryDiffEq's norm under duals, which also weighs the
+ * partials, is not reproduced); the steps are left where cude_adaptive_steps reads them.  A subject with a non-finite
+ * parameter or a failed adaptive solve gets NaN in all its outputs and is counted by cude_n_failed (this rank's
+ * subjects); the others are unaffected.  CUDE_ERR_UNSUPPORTED for a network on the fallback kernel (cude_set_network). */
+int32_t cude_sensitivity(cude_ctx* ctx, double* sens, double* info, double* score, double* sse);
+
 /* Multi-start screening: forward-only loss of n_sets candidate parameter sets over the resident
  * population in one launch (first phase of `train`, src/parameter-estimation.jl:351-366;
  * fit_suppression_model suppression_model.jl:135; c-peptide/06-saem.jl:41-42).
