@@ -207,6 +207,7 @@ const OptionEntry kOptions[] = {
     {"prio_shift", "CUDE_PRIO_SHIFT", &Options::prio_shift, false, true},
     {"dense_chunk", "CUDE_DENSE_CHUNK", &Options::dense_chunk, false, false},
     {"dense_layout", "CUDE_DENSE_LAYOUT", &Options::dense_layout, false, false},
+    {"refine_fused", "CUDE_REFINE_FUSED", &Options::refine_fused, false, false},
 };
 }  // namespace
 

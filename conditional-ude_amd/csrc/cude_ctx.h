@@ -87,6 +87,8 @@ struct Options {
     int dense_chunk = 0;        // "dense_chunk" / CUDE_DENSE_CHUNK: cude_simulate's output times per launch (0 = ~1 GB of scratch)
     int dense_layout = 0;       // "dense_layout" / CUDE_DENSE_LAYOUT: suppression dense output written straight into the caller's
                                 //   [3 x T x N] (0, measured faster: cude_simulate) or lane-contiguous [T][3][N] + a transpose (1)
+    int refine_fused = 1;       // "refine_fused" / CUDE_REFINE_FUSED: cude_refine_conditional in fixed-step mode as ONE launch (1) or as one
+                                //   tangent launch + one update launch per evaluation (0: the form the adaptive mode always runs)
     // ("hidden_activation" = tanh | relu | sigmoid, "output_activation" = softplus | identity: kept in cude_ctx::net)
     // ---- ablation
     int mixed = 1;              // CUDE_NO_MIXED
@@ -152,6 +154,8 @@ struct cude_ctx {
     // parameters / gradients / optimiser
     cude::api::DevBuf<double> nn, cond, g_nn, g_cond, sse, auc, partials, traj;
     cude::api::DevBuf<double> sens, sens_info, sens_score;     // cude_sensitivity: [n_state x T x N], [N], [N] (first call)
+    cude::api::DevBuf<double> refine_buf;                      // cude_refine_conditional: 13 rows of N (first call; kept, so that
+    cude::api::DevBuf<int32_t> refine_ibuf;                    // ... repeated fits -- SAEM's MAP step -- do not allocate): 2 rows
     // chunked gradient path (cude_cpep2.hip)
     int chunks = 1;
     int n_cu = 256;         // compute units of the device (setup_chunks)

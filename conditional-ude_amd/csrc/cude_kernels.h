@@ -459,6 +459,29 @@ hipError_t launch_fit(int phase, const FitArgs& a, int k, double x, hipStream_t 
 constexpr int kFitSpecMaxDepth = 4;
 hipError_t launch_fit_grid_all(const FitArgs& a, int k0, int kn, const double* values, const double* sse_sets, hipStream_t s);
 hipError_t launch_fit_tree(const FitArgs& a, int depth, int resolve, int final, double* cand, const double* sse_sets, hipStream_t s);
+// per-subject Newton-type fits (cude_refine_conditional, cude_refine.hip): the rule's constants and the search state, all
+// arrays [N] at the subjects' own indices.  The fused kernels read xt (the clamped start is formed from x0) and write the
+// six result arrays; the stepped form keeps the whole state on the device between its rounds.
+constexpr int kRefineRunning = -1;                // (results: CUDE_REFINE_* of include/cude.h)
+struct RefineCfg {
+    double lower, upper, xtol, max_step;
+    double pw, pc;                                // penalty pw (x - pc)^2
+    int32_t max_evals;
+};
+struct RefineArrays {
+    int64_t N;
+    const double* x0;                             // starts (not clamped yet)
+    double* x; double* F; double* sse; double* info;      // current point, its objective, SSE and information sum
+    int32_t* evals; int32_t* status;
+    double* g; double* lam; double* xp; double* gp; double* xt;      // stepped form: half gradient, damping, secant pair, trial
+    const double* sse_t; const double* score_t; const double* info_t;   // stepped form: the evaluation at xt
+};
+// fused form (fixed-step mode): hipErrorInvalidValue when no kernel is compiled for the shape
+hipError_t launch_cpep_refine(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
+hipError_t launch_supp_refine(const NetShape& net, const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
+// phase 0 = clamp the starts, 1 = the rule's update behind an evaluation at xt (both: stepped form); 2 = objective at the
+// result from the SSE in r.sse (either form)
+hipError_t launch_refine_step(int phase, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
 hipError_t launch_fill(int64_t N, double v, double* out, hipStream_t s);
 hipError_t launch_fill_rows(int64_t N, int n_rows, const double* values, double* out, hipStream_t s);
 // population preparation

@@ -1332,6 +1332,111 @@ int32_t cude_fit_conditional(cude_ctx* c, double lower, double upper, int32_t n_
     return CUDE_OK;
 }
 
+int32_t cude_refine_conditional(cude_ctx* c, const double* x0, double lower, double upper, int32_t max_evals, double xtol,
+                                double max_step, double penalty_weight, double penalty_center, double* cond_out,
+                                double* objective_out, double* sse_out, double* info_out, int32_t* evals_out,
+                                int32_t* status_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (!x0 && !c->have_cond) return fail(CUDE_ERR_STATE, "no start: conditional parameters not set and x0 is null");
+    if (!(lower < upper) || !std::isfinite(lower) || !std::isfinite(upper)) return fail(CUDE_ERR_ARG, "need finite lower < upper");
+    if (max_evals < 1 || !(xtol > 0) || !(max_step > 0) || !(penalty_weight >= 0) || !std::isfinite(penalty_weight) ||
+        !std::isfinite(penalty_center))
+        return fail(CUDE_ERR_ARG, "need max_evals >= 1, xtol > 0, max_step > 0, finite penalty_weight >= 0");
+    if (!cond_out) return fail(CUDE_ERR_ARG, "null output");
+    if (c->net.generic())
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_refine_conditional: the network of this context runs on the fallback kernel "
+                                          "(cude_set_network), which has no tangent-linear solve");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_refine_conditional under stream capture");
+    const bool cpep = is_cpep(c);
+    const int64_t N = c->N;
+    DevBuf<double>& buf = c->refine_buf;                  // x0, x, F, sse, info, g, lam, xp, gp, xt, sse_t, score_t, info_t
+    DevBuf<int32_t>& ibuf = c->refine_ibuf;               // evals, status
+    HIP_TRY(buf.reserve((size_t)13 * N));
+    HIP_TRY(ibuf.reserve((size_t)2 * N));
+    cude::RefineCfg k{};
+    k.lower = lower; k.upper = upper; k.xtol = xtol; k.max_step = max_step;
+    k.pw = penalty_weight; k.pc = penalty_center; k.max_evals = max_evals;
+    cude::RefineArrays r{};
+    r.N = N;
+    double* q = buf.p;
+    if (x0) {
+        HIP_TRY(hipMemcpyAsync(q, x0, N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        r.x0 = q;
+    } else {
+        r.x0 = c->cond.p;
+    }
+    r.x = q + N; r.F = q + 2 * N; r.sse = q + 3 * N; r.info = q + 4 * N;
+    r.g = q + 5 * N; r.lam = q + 6 * N; r.xp = q + 7 * N; r.gp = q + 8 * N; r.xt = q + 9 * N;
+    double* sse_t = q + 10 * N;
+    double* score_t = q + 11 * N;
+    double* info_t = q + 12 * N;
+    r.sse_t = sse_t; r.score_t = score_t; r.info_t = info_t;
+    r.evals = ibuf.p; r.status = ibuf.p + N;
+    hipError_t le = hipSuccess;
+    if (!adaptive(c) && c->opt.refine_fused) {
+        // the whole iteration of every subject in ONE launch
+        if (cpep) {
+            cude::CpepArgs a = cpep_args(c);
+            a.nn = c->nn.p;
+            le = cude::launch_cpep_refine(c->net, c->cfg.n_state, a, k, r, c->stream);
+        } else {
+            cude::SuppArgs a = supp_args(c);
+            a.nn = c->nn.p;
+            le = cude::launch_supp_refine(c->net, a, k, r, c->stream);
+        }
+    } else {
+        // per evaluation a tangent launch at the trial points and the rule's update; every round is queued, the subjects that
+        // have stopped keep their state (and are solved along at their last trial point)
+        HIP_TRY(cude::launch_refine_step(0, k, r, c->stream));
+        cude::SensOut out;
+        out.info = info_t;
+        out.score = score_t;
+        for (int it = 0; it < max_evals && le == hipSuccess; it++) {
+            if (cpep) {
+                cude::CpepSensArgs a{};
+                static_cast<cude::CpepArgs&>(a) = cpep_args(c);
+                a.cond = r.xt; a.nn = c->nn.p; a.sse = sse_t; a.partials = c->partials.p; a.tape = nullptr;
+                a.out = out;
+                le = cude::launch_cpep_sens(c->net, c->cfg.n_state, a, c->stream);
+            } else {
+                cude::SuppSensArgs a{};
+                static_cast<cude::SuppArgs&>(a) = supp_args(c);
+                a.cond = r.xt; a.nn = c->nn.p; a.sse = sse_t; a.partials = c->partials.p; a.tape = nullptr;
+                a.out = out;
+                le = cude::launch_supp_sens(c->net, a, c->stream);
+            }
+            if (le == hipSuccess) le = cude::launch_refine_step(1, k, r, c->stream);
+        }
+        // (adaptive mode: nothing of these solves is on the gradient's tape -- cude_adaptive_steps refuses afterwards)
+        if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
+    }
+    if (le == hipErrorInvalidValue)
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_refine_conditional: no tangent kernel compiled for this network shape / model");
+    HIP_TRY(le);
+    // The SSE that is REPORTED is cude_forward's own at the returned point, as cude_fit_conditional's is (one forward launch
+    // behind the iteration): the tangent sweep's SSE agrees with it to a few 1e-17 absolute, which on a near-perfect fit
+    // (SSE ~ 1e-5) is 2e-12 relative -- callers compare these numbers across entry points.
+    if ((rc = run_ensemble(c, false, nullptr, true, r.x, r.sse))) return rc;
+    HIP_TRY(cude::launch_refine_step(2, k, r, c->stream));
+    if (adaptive(c)) c->have_tape = false;
+    std::vector<int32_t> status((size_t)N);
+    HIP_TRY(hipMemcpyAsync(cond_out, r.x, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (objective_out) HIP_TRY(hipMemcpyAsync(objective_out, r.F, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (sse_out) HIP_TRY(hipMemcpyAsync(sse_out, r.sse, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (info_out) HIP_TRY(hipMemcpyAsync(info_out, r.info, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (evals_out) HIP_TRY(hipMemcpyAsync(evals_out, r.evals, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status.data(), r.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t n_failed = 0;
+    for (int64_t i = 0; i < N; i++) n_failed += status[(size_t)i] == CUDE_REFINE_FAILED;
+    c->last_failed = n_failed;
+    if (status_out) std::memcpy(status_out, status.data(), (size_t)N * sizeof(int32_t));
+    return CUDE_OK;
+}
+
 }  // extern "C"
 
 namespace {

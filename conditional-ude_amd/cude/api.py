@@ -672,7 +672,7 @@ def _batched_adam_then_lbfgs(eng, nn_inits, cond_inits, adam_iters, lbfgs_iters,
 def train(models, timepoints, cpeptide_data, rng_or_nn, *, initial_guesses=None, selected_initials=None,
           lhs_lower_bound=-2.0, lhs_upper_bound=0.0, n_conditional_parameters=1, number_of_iterations_adam=1000,
           number_of_iterations_lbfgs=1000, learning_rate_adam=1e-2, initial_beta=-2.0, lbfgs_lower_bound=-4.0,
-          lbfgs_upper_bound=1.0, lbfgs_iterations=1000, n_steps=None, side_by_side=True):
+          lbfgs_upper_bound=1.0, lbfgs_iterations=1000, n_steps=None, side_by_side=True, method="search"):
     """Three methods of the reference, selected by the types of the 1st and 4th argument as Julia's dispatch does:
     * a single CPeptideUDEModel + rng: the conventional UDE on one (mean) subject (:205-247): `initial_guesses`
       (default 10 000) initialisations screened by their loss, the best `selected_initials` (10) -> Adam -> L-BFGS.
@@ -681,7 +681,7 @@ def train(models, timepoints, cpeptide_data, rng_or_nn, *, initial_guesses=None,
       restarts are trained side by side (one launch per optimiser iteration for all of them) unless
       side_by_side=False.
     * array of network parameters: per-subject estimation of the conditional parameter with the network
-      frozen (:272-288)."""
+      frozen (:272-288); `method` as estimate_conditional."""
     if isinstance(models, CPeptideUDEModel):
         return _train_ude(models, timepoints, cpeptide_data, rng_or_nn,
                           initial_guesses=10_000 if initial_guesses is None else initial_guesses,
@@ -731,7 +731,7 @@ def train(models, timepoints, cpeptide_data, rng_or_nn, *, initial_guesses=None,
         return sols
     nn = np.asarray(rng_or_nn, dtype=np.float64)
     beta, sse = estimate_conditional(models, timepoints, cpeptide_data, nn, initial_beta=initial_beta,
-                                     lower=lbfgs_lower_bound, upper=lbfgs_upper_bound, n_steps=n_steps)
+                                     lower=lbfgs_lower_bound, upper=lbfgs_upper_bound, n_steps=n_steps, method=method)
     return [OptimizationSolution(u=np.array([b]), objective=s) for b, s in zip(beta, sse)]
 
 
@@ -769,26 +769,51 @@ def _train_ude(model, timepoints, cpeptide_data, rng, *, initial_guesses, select
     return sols
 
 
+def _fit_box(eng, lower, upper, n_grid, iters, method, *, start=None, penalty_weight=0.0, penalty_center=0.0,
+             max_evals=40):
+    """The per-subject fits behind every frozen-network estimate: (x, objective, sse, info or None).
+    method = "search": cude_fit_conditional (coarse scan + golden section), today's behaviour bit for bit.
+    method = "newton": the coarse scan as ONE profile launch (n_grid values), then cude_refine_conditional from every
+    subject's argmin; n_grid = 0: no scan, the refinement starts from `start` (scalar or (N,)) -- the reference's own
+    semantics of a local solver from an initial point."""
+    if method == "search":
+        return eng.fit_conditional(lower, upper, n_grid, iters, penalty_weight, penalty_center) + (None,)
+    if method != "newton":
+        raise ValueError(f'method must be "search" or "newton", not {method!r}')
+    if n_grid > 0:
+        values = np.linspace(lower, upper, n_grid)
+        prof = eng.profile_conditional(values) + penalty_weight * (values[:, None] - penalty_center) ** 2
+        start = values[np.argmin(np.where(np.isfinite(prof), prof, np.inf), axis=0)]
+        del prof            # (a multi-megabyte read-back kept alive across the next call was measured to stall it)
+    elif start is None:
+        raise ValueError("n_grid = 0 needs a start")
+    r = eng.refine_conditional(np.asarray(start, dtype=np.float64), lower, upper, max_evals=max_evals,
+                               penalty_weight=penalty_weight, penalty_center=penalty_center)
+    return r["x"], r["objective"], r["sse"], r["info"]
+
+
 def estimate_conditional(models, timepoints, cpeptide_data, nn, *, initial_beta=-2.0, lower=-4.0, upper=1.0,
-                         n_steps=None, n_grid=41, iters=48):
-    """All N independent 1-D problems min_beta SSE_i(beta) at once (cude_fit_conditional: coarse scan + golden
-    section with the search state on the device, one forward launch over the population per probe).  Box
-    [lower, upper]; infinite bounds are replaced by initial_beta -/+ 6.  Returns (beta[N], SSE[N])."""
+                         n_steps=None, n_grid=41, iters=48, method="search", return_info=False):
+    """All N independent 1-D problems min_beta SSE_i(beta) at once.  Box [lower, upper]; infinite bounds are replaced by
+    initial_beta -/+ 6.  method = "search" (cude_fit_conditional: coarse scan + golden section with the search state on
+    the device, one forward launch over the population per probe) or "newton" (one profile launch of n_grid values, then
+    cude_refine_conditional from every subject's argmin; n_grid = 0: from initial_beta, as the reference's LBFGS run).
+    Returns (beta[N], SSE[N]), with return_info also info[N] at the result ("newton": the fit's own; "search": None)."""
     pop = _population(models, timepoints, cpeptide_data, n_steps)
     eng = pop.engine
     lo = lower if np.isfinite(lower) else np.min(initial_beta) - 6.0
     hi = upper if np.isfinite(upper) else np.max(initial_beta) + 6.0
     eng.set_params(nn, None)
-    x, _, sse = eng.fit_conditional(lo, hi, n_grid, iters)
-    return x, sse
+    x, _, sse, info = _fit_box(eng, lo, hi, n_grid, iters, method, start=initial_beta)
+    return (x, sse, info) if return_info else (x, sse)
 
 
 def train_with_sigma(models, timepoints, cpeptide_data, nn, *, initial_beta=-2.0, lbfgs_lower_bound=-4.0,
-                     lbfgs_upper_bound=1.0, lbfgs_iterations=1000, n_steps=None):
+                     lbfgs_upper_bound=1.0, lbfgs_iterations=1000, n_steps=None, method="search"):
     """Joint (beta, sigma) estimate per subject (:290-307).  For fixed beta the NLL is minimised by
-    sigma^2 = SSE/n, and beta minimises SSE, so the 2-D problem separates."""
+    sigma^2 = SSE/n, and beta minimises SSE, so the 2-D problem separates.  `method` as estimate_conditional."""
     beta, sse = estimate_conditional(models, timepoints, cpeptide_data, nn, initial_beta=initial_beta,
-                                     lower=lbfgs_lower_bound, upper=lbfgs_upper_bound, n_steps=n_steps)
+                                     lower=lbfgs_lower_bound, upper=lbfgs_upper_bound, n_steps=n_steps, method=method)
     n = len(timepoints)
     sigma = np.sqrt(np.maximum(sse, 1e-300) / n)
     obj = (n / 2) * np.log(sigma ** 2) + sse / (2 * sigma ** 2)
@@ -877,11 +902,14 @@ def sensitivities(theta, args, *, n_steps=None):
 
 
 def conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data, *, sigma=None,
-                                n_steps=None):
+                                n_steps=None, info=None, sse=None):
     """Asymptotic standard error of every subject's conditional parameter: sigma / sqrt(info_i), the inverse square root
     of the Fisher information info_i / sigma^2 of a Gaussian error model.  sigma = None: the per-subject maximum-likelihood
     value sigma_i^2 = SSE_i / n_i, the closed form loss_sigma (src/parameter-estimation.jl:70-75) is minimised by.  A
-    subject whose data do not identify the parameter (info = 0) gets inf."""
+    subject whose data do not identify the parameter (info = 0) gets inf.  info (and sse, unless sigma is given): what a
+    fit with method = "newton" returned at betas (estimate_conditional(..., return_info=True)) -- no second solve."""
+    if info is not None and (sigma is not None or sse is not None):
+        return _standard_errors(info, np.zeros_like(info) if sse is None else sse, len(timepoints), sigma)
     theta = ComponentArray(neural=neural_network_parameters, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
     _, info, _, sse = sensitivities(theta, (models, timepoints, cpeptide_data), n_steps=n_steps)
     return _standard_errors(info, sse, len(timepoints), sigma)
@@ -1076,19 +1104,20 @@ def fit_suppression_model(p_init, prob, data, timepoints, lam, *, select_best_n=
 
 
 def validate_suppression_model(p_init, prob, data, timepoints, network_params, *, n_steps=None, lower=-8.0,
-                               upper=5.0):
+                               upper=5.0, method="search"):
     """validate_suppression_model(p_init, prob, data, timepoints, network_params) (:179-222): conditional parameters
     of new subjects with the network frozen, returns (theta, objective).  With the network fixed the loss separates
     per subject, so instead of one L-BFGS run from the best of `p_init` all subjects are solved together by a
     bracketing search over [lower, upper] (one forward launch per probe) -- the global minimum per subject, hence an
-    objective <= the reference's.  p_init is accepted for signature compatibility and only widens the bracket."""
+    objective <= the reference's.  p_init is accepted for signature compatibility and only widens the bracket.
+    method = "newton": the 161-point scan as one profile launch, then cude_refine_conditional from every argmin."""
     pop = _supp_population(prob, data, timepoints, 0.0, n_steps)
     eng, N = pop.engine, np.asarray(data).shape[2]
     if p_init is not None and len(p_init):
         lower = min(lower, float(np.min(p_init)))
         upper = max(upper, float(np.max(p_init)))
     eng.set_params(network_params, None)
-    theta, _, best = eng.fit_conditional(lower, upper, 161, 48)
+    theta, _, best, _ = _fit_box(eng, lower, upper, 161, 48, method)
     return theta, float(best.sum() / N)
 
 
@@ -1183,11 +1212,12 @@ def map_objective(p_individual, sse, n_obs, sigma, omega, *, prior_individual=0.
 
 
 def compute_individual_maps(p_individuals, p_neural, models, timepoints, cpeptide_data, sigma, omega, *,
-                            prior_individual=0.0, lower=-6.0, upper=4.0, n_steps=None):
+                            prior_individual=0.0, lower=-6.0, upper=4.0, n_steps=None, method="search"):
     """compute_individual_maps (src/saem.jl:74-84): every subject's maximum-a-posteriori conditional parameter with
     the network frozen.  argmin_x -(ll + logprior) = argmin_x SSE(x) + (sigma / omega)^2 (x - prior)^2: one penalised
     per-subject search on the device for all subjects (cude_fit_conditional) instead of an L-BFGS run per subject;
-    p_individuals (the reference's starting points) only widen the bracket."""
+    p_individuals (the reference's starting points) only widen the bracket.  method = "newton": they ARE the starting
+    points of cude_refine_conditional, as in the reference (none given: an 81-point scan first)."""
     models = [models] if _is_model(models) else list(models)
     data = np.asarray(cpeptide_data, dtype=np.float64)
     data = data[None, :] if data.ndim == 1 else data
@@ -1196,8 +1226,10 @@ def compute_individual_maps(p_individuals, p_neural, models, timepoints, cpeptid
         lower = min(lower, float(np.min(p_individuals)))
         upper = max(upper, float(np.max(p_individuals)))
     pop.engine.set_params(p_neural, None)
-    x, _, _ = pop.engine.fit_conditional(lower, upper, 81, 48, penalty_weight=(sigma / omega) ** 2,
-                                         penalty_center=prior_individual)
+    have_start = p_individuals is not None and np.size(p_individuals)
+    start = np.asarray(p_individuals, dtype=np.float64).reshape(-1) if have_start else None
+    x, _, _, _ = _fit_box(pop.engine, lower, upper, 0 if (method == "newton" and have_start) else 81, 48, method,
+                          start=start, penalty_weight=(sigma / omega) ** 2, penalty_center=prior_individual)
     return x
 
 
@@ -1276,18 +1308,19 @@ def individual_effects(models, timepoints, cpeptide_data, saem_result, *, n_samp
 
 
 # ----------------------------------------------------------------------------- symbolic (Michaelis-Menten) model
-def train_symbolic(models, timepoints, cpeptide_data, *, lower=0.0, upper=1000.0, n_steps=None):
+def train_symbolic(models, timepoints, cpeptide_data, *, lower=0.0, upper=1000.0, n_steps=None, method="search"):
     """The per-subject loop of c-peptide/03-symreg.jl:94-106: minimise loss_sigma over (k, sigma) with
     0 <= k <= 1000 for every CPeptideODEModel.  For fixed k the optimum is sigma^2 = SSE/n, and k minimises the
     SSE, so all N problems are solved together by a bracketing search on log k (one forward launch per probe).
-    Returns OptimizationSolution(u = ComponentArray(ode=[k], sigma), objective) per subject."""
+    Returns OptimizationSolution(u = ComponentArray(ode=[k], sigma), objective) per subject.  method = "newton": the
+    61-point scan as one profile launch, then cude_refine_conditional from every argmin."""
     pop = _population(models, timepoints, cpeptide_data, n_steps, cond_space="log")
     eng, N = pop.engine, pop.N
     eng.set_params(pop.shared, np.zeros(N))
     lo = math.log(max(lower, 1e-6))
     hi = math.log(upper)
 
-    logk, _, val = eng.fit_conditional(lo, hi, 61, 48)
+    logk, _, val, _ = _fit_box(eng, lo, hi, 61, 48, method)
     n = len(timepoints)
     sigma = np.sqrt(np.maximum(val, 1e-300) / n)
     obj = (n / 2) * np.log(sigma ** 2) + val / (2 * sigma ** 2)

@@ -57,6 +57,9 @@ def lbfgs_minimize(fg, x0, maxiters=1000):
 _CANDIDATES = C.CFUNCTYPE(C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
 _REDUCE = C.CFUNCTYPE(C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_void_p)
 
+# status codes of Engine.refine_conditional (CUDE_REFINE_* of include/cude.h)
+REFINE_CONVERGED, REFINE_AT_BOUND, REFINE_MAX_EVALS, REFINE_FLAT, REFINE_FAILED = range(5)
+
 
 def lbfgs_minimize_sharded(fg, x0, n_shared, reduce, maxiters=1000):
     """cude_lbfgs_minimize_sharded: x = [shared (n_shared, replicated); local]; fg(x) -> (global f, local g);
@@ -380,6 +383,21 @@ class Engine:
                                              float(penalty_weight), float(penalty_center), _ptr(x), _ptr(obj),
                                              _ptr(sse)))
         return x, obj, sse
+
+    def refine_conditional(self, x0=None, lower=-4.0, upper=3.0, max_evals=40, xtol=1e-7, max_step=0.5,
+                           penalty_weight=0.0, penalty_center=0.0):
+        """The same problems by the Newton-type iteration of cude_refine_conditional from the starts x0 (N,) -- None:
+        the context's conditional parameters -- in one launch (fixed-step mode): dict(x, objective, sse, info (N,)
+        doubles; evals, status (N,) int32, status = REFINE_*).  A failed subject keeps its clamped start, objective +Inf."""
+        if x0 is not None:
+            x0 = np.ascontiguousarray(np.broadcast_to(_f64(x0), (self.N,)))
+        x, obj, sse, info = np.empty(self.N), np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        evals, status = np.empty(self.N, dtype=np.int32), np.empty(self.N, dtype=np.int32)
+        check(self._lib.cude_refine_conditional(self._h, _ptr(x0), float(lower), float(upper), int(max_evals),
+                                                float(xtol), float(max_step), float(penalty_weight),
+                                                float(penalty_center), _ptr(x), _ptr(obj), _ptr(sse), _ptr(info),
+                                                _ptr(evals), _ptr(status)))
+        return {"x": x, "objective": obj, "sse": sse, "info": info, "evals": evals, "status": status}
 
     def mh_chain(self, normals, uniforms, sigma, prior_mean, prior_sd, proposal_std, temperature=1.0, gamma=1.0,
                  n_mc=None):

@@ -206,6 +206,43 @@ function fit_conditional(c::Ctx, lower, upper; n_grid = 41, n_iters = 48, penalt
     β, obj, sse
 end
 
+# the same problems by the Newton-type iteration of cude_refine_conditional from the starts x0 (nothing: the context's
+# conditional parameters), one launch in fixed-step mode; returns (x, objective, SSE, info, evals, status = REFINE_*)
+const REFINE_CONVERGED, REFINE_AT_BOUND, REFINE_MAX_EVALS, REFINE_FLAT, REFINE_FAILED = 0, 1, 2, 3, 4
+function refine_conditional(c::Ctx, x0, lower, upper; max_evals = 40, xtol = 1e-7, max_step = 0.5, penalty_weight = 0.0,
+                            penalty_center = 0.0)
+    x = Vector{Float64}(undef, c.N); obj = similar(x); sse = similar(x); info = similar(x)
+    evals = Vector{Int32}(undef, c.N); status = Vector{Int32}(undef, c.N)
+    start = x0 === nothing ? nothing : (x0 isa Real ? fill(Float64(x0), c.N) : Vector{Float64}(x0))
+    GC.@preserve start x obj sse info evals status check(ccall((:cude_refine_conditional, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Float64, Float64, Int32, Float64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+        c.h, start === nothing ? C_NULL : pointer(start), lower, upper, max_evals, xtol, max_step, penalty_weight,
+        penalty_center, x, obj, sse, info, evals, status))
+    x, obj, sse, info, evals, status
+end
+
+# the two ways of solving the per-subject problems behind every frozen-network estimate (keyword `method`): `search` =
+# fit_conditional (coarse scan + golden section, the default), `newton` = the scan as one profile launch, then
+# refine_conditional from every subject's argmin (n_grid = 0: from `start`, the reference's local solve from a point)
+const search = :search
+const newton = :newton
+function fit_box(c::Ctx, lower, upper, n_grid, method; start = nothing, penalty_weight = 0.0, penalty_center = 0.0)
+    if method == search
+        return (fit_conditional(c, lower, upper; n_grid = n_grid, penalty_weight = penalty_weight,
+                                penalty_center = penalty_center)..., nothing)
+    end
+    method == newton || error("method must be search or newton")
+    if n_grid > 0
+        values = collect(Float64, range(lower, stop = upper, length = n_grid))
+        prof = profile_conditional(c, values) .+ penalty_weight .* (values' .- penalty_center) .^ 2
+        start = [values[argmin(map(v -> isfinite(v) ? v : Inf, prof[i, :]))] for i in 1:c.N]
+    end
+    x, obj, sse, info, _, _ = refine_conditional(c, start, lower, upper; penalty_weight = penalty_weight,
+                                                 penalty_center = penalty_center)
+    x, obj, sse, info
+end
+
 # SSE_i(values[k]) as an N×K matrix
 function profile_conditional(c::Ctx, values::Vector{Float64})
     sse = Matrix{Float64}(undef, c.N, length(values))
@@ -754,12 +791,13 @@ end
 # train(models, timepoints, cpeptide_data, neural_network_parameters; ...) (:272-288): every subject's β at once
 function train(models::AbstractVector{CPeptideConditionalUDEModel}, timepoints::AbstractVector{T},
                cpeptide_data::AbstractMatrix{T}, neural_network_parameters::AbstractVector{T};
-               initial_beta = -2.0, lbfgs_lower_bound = -4.0, lbfgs_upper_bound = 1.0, lbfgs_iterations::Int = 1000) where T<:Real
+               initial_beta = -2.0, lbfgs_lower_bound = -4.0, lbfgs_upper_bound = 1.0, lbfgs_iterations::Int = 1000,
+               method = search) where T<:Real
     c = population(models, timepoints, cpeptide_data)
     set_params!(c, neural_network_parameters, nothing)
     lo = isfinite(lbfgs_lower_bound) ? lbfgs_lower_bound : initial_beta - 6.0
     hi = isfinite(lbfgs_upper_bound) ? lbfgs_upper_bound : initial_beta + 6.0
-    β, _, sse = fit_conditional(c, lo, hi)
+    β, _, sse, _ = fit_box(c, lo, hi, 41, method; start = initial_beta)
     [Solution([β[i]], sse[i]) for i in eachindex(β)]
 end
 
@@ -767,9 +805,9 @@ end
 function train_with_sigma(models::AbstractVector{CPeptideConditionalUDEModel}, timepoints::AbstractVector{T},
                           cpeptide_data::AbstractMatrix{T}, neural_network_parameters::AbstractVector{T};
                           initial_beta = -2.0, lbfgs_lower_bound = -4.0, lbfgs_upper_bound = 1.0,
-                          lbfgs_iterations::Int = 1000) where T<:Real
+                          lbfgs_iterations::Int = 1000, method = search) where T<:Real
     sols = train(models, timepoints, cpeptide_data, neural_network_parameters; initial_beta = initial_beta,
-                 lbfgs_lower_bound = lbfgs_lower_bound, lbfgs_upper_bound = lbfgs_upper_bound)
+                 lbfgs_lower_bound = lbfgs_lower_bound, lbfgs_upper_bound = lbfgs_upper_bound, method = method)
     n = length(timepoints)
     map(sols) do s
         σ = sqrt(max(s.objective, 1e-300) / n)
@@ -817,7 +855,11 @@ function standard_errors(info, sse, n_obs, sigma)
 end
 # σ / √infoᵢ; sigma = nothing: σᵢ² = SSEᵢ / nᵢ (the closed form loss_sigma is minimised by); info = 0 -> Inf
 function conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data;
-                                     sigma = nothing, n_steps = nothing)
+                                     sigma = nothing, n_steps = nothing, info = nothing, sse = nothing)
+    # info (and sse, unless sigma is given): what a fit with method = newton returned at betas -- no second solve
+    if info !== nothing && (sigma !== nothing || sse !== nothing)
+        return standard_errors(info, sse === nothing ? zero(info) : sse, length(timepoints), sigma)
+    end
     _, info, _, sse = sensitivities((neural = neural_network_parameters, conditional = betas),
                                     (models, timepoints, cpeptide_data); n_steps = n_steps)
     standard_errors(info, sse, length(timepoints), sigma)
@@ -1000,11 +1042,13 @@ function map_objective(p_individual, p_neural, individual, σ, Ω, network::Chai
     -(ll + prior)
 end
 function compute_individual_maps(p_individuals, p_neural, individuals, σ, Ω, network::Chain; prior_individual = 0.0,
-                                 lower = -6.0, upper = 4.0)
+                                 lower = -6.0, upper = 4.0, method = search)
     c = individuals_population(individuals, network)
     set_params!(c, p_neural, Vector{Float64}(p_individuals))
-    x, _, _ = fit_conditional(c, min(lower, minimum(p_individuals)), max(upper, maximum(p_individuals)); n_grid = 81,
-                              penalty_weight = (σ / Ω)^2, penalty_center = prior_individual)
+    # method = newton: p_individuals ARE the starting points, as in the reference (search: they only widen the bracket)
+    x, _, _, _ = fit_box(c, min(lower, minimum(p_individuals)), max(upper, maximum(p_individuals)),
+                         method == newton ? 0 : 81, method; start = p_individuals, penalty_weight = (σ / Ω)^2,
+                         penalty_center = prior_individual)
     x
 end
 

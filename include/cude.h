@@ -294,6 +294,43 @@ int32_t cude_fit_conditional(cude_ctx* ctx, double lower, double upper, int32_t 
                              double penalty_weight, double penalty_center, double* cond_out, double* objective_out,
                              double* sse_out);
 
+/* The same per-subject problems by a LOCAL, gradient-based method from a given start -- what the reference's own solver
+ * is (`LBFGS` inside `Fminbox` from `initial_beta`, under ForwardDiff: src/parameter-estimation.jl:272-307, :406-433;
+ * suppression_model.jl:179-222; c-peptide/03-symreg.jl:94-106; `compute_individual_maps`, src/saem.jl:74-84).  Subject i
+ * minimises  F(x) = SSE_i(x) + penalty_weight * (x - penalty_center)^2  over [lower, upper] from x0_i by a damped
+ * Newton-type iteration whose every evaluation is one tangent-linear solve (cude_sensitivity's sse, score, info):
+ * g = score + pw (x - pc), Hgn = info + pw.
+ *   1. x = clamp(x0, lower, upper); evaluate; lambda = 1e-3; no secant pair yet.  Non-finite F: FAILED.
+ *   2. c = (g - gp) / (x - xp) over the secant pair (xp, gp); H = c if finite and > 0, else Hgn.  Not H > 0: FLAT.
+ *   3. d = clamp(-g / (H (1 + lambda)), +-max_step); xt = clamp(x + d, lower, upper).
+ *   4. |xt - x| <= xtol (1 + |x|): AT_BOUND if xt is a bound, else CONVERGED.
+ *   5. evaluate at xt; accept iff F(xt) is finite and < F.  Accept: (xp, gp) <- (x, g), move to xt, lambda <-
+ *      max(lambda / 10, 1e-12).  Reject: (xp, gp) <- (xt, g(xt)) if F(xt) was finite; lambda <- 10 lambda.
+ *   6. evals == max_evals: MAX_EVALS (also right after step 1 when max_evals == 1); otherwise back to 2.
+ * Fixed-step mode: ONE launch -- a lane iterates its subject until it stops, a wave retires with its slowest lane
+ * (option "refine_fused" = 0: one tangent launch + one update launch per evaluation instead, which is also what the
+ * adaptive mode always runs; all max_evals rounds are queued, one synchronisation at the end).
+ * xtol: the acceptance test of step 5 compares two objective values, so steps shorter than the width over which the SSE is
+ * flat to rounding (~1e-7 in x for the reference's problems) are accepted or rejected by rounding noise; the mirrors'
+ * default is 1e-7, where the result is reproducible to ~1e-14 under the tangent kernels' accepted error.
+ * x0 [N], or NULL = the context's conditional parameters.  Outputs, all [N], all optional but cond_out: the point
+ * reached, its objective, its SSE, cude_sensitivity's info at it, the number of evaluations and the CUDE_REFINE_* status.
+ * sse_out is cude_forward's own number at cond_out (one forward launch behind the iteration, as cude_fit_conditional's)
+ * and objective_out = sse_out + penalty; the tangent solve's SSE, which the iteration compares, agrees with it to rounding.
+ * A FAILED subject returns its clamped start and objective +Inf, does not disturb the others and is counted by
+ * cude_n_failed.  Uses the context's shared parameters, leaves its conditional parameters untouched.  Adaptive mode:
+ * cude_adaptive_steps refuses afterwards (the last solve was of a trial point).  CUDE_ERR_UNSUPPORTED for a network on
+ * the fallback kernel (cude_set_network), CUDE_ERR_STATE under stream capture. */
+#define CUDE_REFINE_CONVERGED 0
+#define CUDE_REFINE_AT_BOUND 1
+#define CUDE_REFINE_MAX_EVALS 2
+#define CUDE_REFINE_FLAT 3
+#define CUDE_REFINE_FAILED 4
+int32_t cude_refine_conditional(cude_ctx* ctx, const double* x0, double lower, double upper, int32_t max_evals,
+                                double xtol, double max_step, double penalty_weight, double penalty_center,
+                                double* cond_out, double* objective_out, double* sse_out, double* info_out,
+                                int32_t* evals_out, int32_t* status_out);
+
 /* SAEM E-step on the device: n_mc Metropolis-Hastings steps of every subject's conditional parameter
  * (`mcmc_step` src/saem.jl:86-108, applied n_mcmc_steps times with the stochastic-approximation update of the
  * chain state :177-186).  The chain state is the context's conditional parameters (updated in place); the
@@ -470,9 +507,10 @@ int32_t cude_xchg_info(cude_ctx* ctx, int32_t* n_ranks, int32_t* rank, int32_t* 
  * launch pair in cude_mh_estep / cude_mh_chain: 0 off, 2 ... 4, -1 = by population size; the chain is the same bit for bit),
  * "dense_chunk" (cude_simulate: output times per launch, 0 = ~1 GB of scratch; tests force several launches with it),
  * "dense_layout" (cude_simulate, suppression model: 0 = the caller's layout written directly, the default; 1 =
- * lane-contiguous rows + a transpose kernel).  Values are decimal integers as text unless noted.  Every option is also read once
+ * lane-contiguous rows + a transpose kernel), "refine_fused" (cude_refine_conditional in fixed-step mode: 1 = the one-launch
+ * kernel, the default; 0 = one tangent launch per evaluation).  Values are decimal integers as text unless noted.  Every option is also read once
  * at cude_create from its environment variable (CUDE_CPEP_PATH, CUDE_CPEP_KEEP, CUDE_SUPP_STORE, CUDE_SUPP_CKPT,
- * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT).
+ * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED).
  * Options that shape the launch path take effect at the next cude_set_population_*.  No reference line: these are
  * properties of this implementation. */
 int32_t cude_set_option(cude_ctx* ctx, const char* name, const char* value);
