@@ -64,12 +64,11 @@ static hipError_t launch_adaptive_out(const SuppArgs& a, hipStream_t s) {
 // the one-body kernel of the suppression shapes the unrolled kernel does not cover (cude_adaptive.h CUDE_SUPP_AD_UNROLLED
 // lists those it does; A/B builds with -DCUDE_ADAPT_ONE_BODY compile them here as well)
 #ifdef CUDE_ADAPT_ONE_BODY
-#define CUDE_SUPP_AD_SHAPES(X) X(3, 5) X(3, 2) X(4, 2) X(6, 2) X(5, 2) X(3, 3) X(8, 2) X(3, 4) X(4, 3) X(4, 4) X(5, 3) X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
+#define CUDE_SUPP_AD_SHAPES(X) CUDE_SUPP_SHAPES(X)
 #else
 #define CUDE_SUPP_AD_SHAPES(X) X(4, 2) X(6, 2) X(5, 2) X(8, 2) X(4, 3) X(4, 4) X(5, 3) X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
 #endif
 
-// (the shapes compiled with the other activation functions: as CUDE_CPEP_GENERAL_SHAPES / CUDE_SUPP_GENERAL_SHAPES)
 template <int NIN, int W, int D>
 static hipError_t launch_cpep_adaptive_general(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
 #define Y(HA, OA) \
@@ -104,13 +103,13 @@ hipError_t launch_cpep_adaptive(const NetShape& net, bool grad, const CpepArgs& 
                           : launch_adaptive<CpepAd<MmProd<false>>, true>(a, a.TG, grad, s);
     if (net.general()) {
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_adaptive_general<NIN, W, D>(net, grad, a, s);
-        X(2, 4, 2) X(2, 6, 2) X(3, 4, 2)
+        CUDE_CPEP_GENERAL_SHAPES(X)
 #undef X
         return hipErrorInvalidValue;
     }
 #define X(NIN, W, D) \
     if (net.nin == NIN && net.width == W && net.depth == D) return launch_adaptive<CpepAd<Mlp<NIN, W, D, 1>>, true>(a, a.TG, grad, s);
-    CUDE_CPEP_AD_SHAPES_0(X)
+    CUDE_CPEP_SHAPES_0(X)
 #undef X
     hipError_t e = launch_cpep_adaptive_part1(net, grad, a, s);
     if (e == hipErrorNotSupported) e = launch_cpep_adaptive_part2(net, grad, a, s);
@@ -127,7 +126,7 @@ hipError_t launch_supp_adaptive(const NetShape& net, bool grad, const SuppArgs& 
 #endif
     if (net.general()) {
 #define X(W, D) if (net.width == W && net.depth == D) return launch_supp_adaptive_general<W, D>(net, grad, a, s);
-        X(3, 5) X(3, 3)
+        CUDE_SUPP_GENERAL_SHAPES(X)
 #undef X
         return hipErrorInvalidValue;
     }
@@ -142,7 +141,7 @@ hipError_t launch_supp_adaptive(const NetShape& net, bool grad, const SuppArgs& 
 hipError_t launch_cpep_adaptive_part1(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
 #define X(NIN, W, D) \
     if (net.nin == NIN && net.width == W && net.depth == D) return launch_adaptive<CpepAd<Mlp<NIN, W, D, 1>>, true>(a, a.TG, grad, s);
-    CUDE_CPEP_AD_SHAPES_1(X)
+    CUDE_CPEP_SHAPES_1(X)
 #undef X
     return hipErrorNotSupported;
 }
@@ -150,7 +149,7 @@ hipError_t launch_cpep_adaptive_part1(const NetShape& net, bool grad, const Cpep
 hipError_t launch_cpep_adaptive_part2(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
 #define X(NIN, W, D) \
     if (net.nin == NIN && net.width == W && net.depth == D) return launch_adaptive<CpepAd<Mlp<NIN, W, D, 1>>, true>(a, a.TG, grad, s);
-    CUDE_CPEP_AD_SHAPES_2(X)
+    CUDE_CPEP_SHAPES_2(X)
 #undef X
     return hipErrorNotSupported;
 }

@@ -429,7 +429,7 @@ hipError_t launch_cpep_adaptive_team(const NetShape& net, bool grad, const CpepA
     if (grad && a.obs == nullptr) return hipErrorInvalidValue;
 #define X(NIN, W, D) \
     if (net.nin == NIN && net.width == W && net.depth == D) return launch_team<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_AD_SHAPES_0(X)
+    CUDE_CPEP_SHAPES_0(X)
 #undef X
     return hipErrorNotSupported;
 }

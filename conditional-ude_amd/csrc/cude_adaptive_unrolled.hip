@@ -361,7 +361,7 @@ hipError_t launch_cpep_adaptive_unrolled(const NetShape& net, bool grad, const C
         return a.cond_raw ? launch_unrolled<CpepAd<MmProd<true>>>(a, grad, s) : launch_unrolled<CpepAd<MmProd<false>>>(a, grad, s);
 #define X(NIN, W, D) \
     if (net.nin == NIN && net.width == W && net.depth == D) return launch_unrolled<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_AD_SHAPES_0(X)
+    CUDE_CPEP_SHAPES_0(X)
 #undef X
     const hipError_t e = launch_cpep_adaptive_unrolled_part1(net, grad, a, s);
     return e != hipErrorNotSupported ? e : launch_cpep_adaptive_unrolled_part2(net, grad, a, s);
@@ -370,7 +370,7 @@ hipError_t launch_cpep_adaptive_unrolled(const NetShape& net, bool grad, const C
 hipError_t launch_cpep_adaptive_unrolled_part1(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
 #define X(NIN, W, D) \
     if (net.nin == NIN && net.width == W && net.depth == D) return launch_unrolled<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_AD_SHAPES_1(X)
+    CUDE_CPEP_SHAPES_1(X)
 #undef X
     return hipErrorNotSupported;
 }
@@ -378,7 +378,7 @@ hipError_t launch_cpep_adaptive_unrolled_part1(const NetShape& net, bool grad, c
 hipError_t launch_cpep_adaptive_unrolled_part2(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
 #define X(NIN, W, D) \
     if (net.nin == NIN && net.width == W && net.depth == D) return launch_unrolled<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_AD_SHAPES_2(X)
+    CUDE_CPEP_SHAPES_2(X)
 #undef X
     return hipErrorNotSupported;
 }

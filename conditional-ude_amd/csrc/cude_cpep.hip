@@ -433,11 +433,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KEEP != 
 }
 
 // ------------------------------------------------------------------------------------ dispatch
-#define CUDE_CPEP_SHAPES(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2) X(2, 8, 2) X(2, 4, 3) X(2, 3, 2) X(2, 5, 2) X(2, 7, 2) X(3, 6, 2) X(2, 4, 1) X(2, 6, 1) X(2, 6, 3) X(2, 8, 1) X(2, 8, 3) X(3, 8, 2) X(2, 3, 1) X(2, 5, 1) X(2, 7, 1) X(2, 3, 3) X(2, 5, 3) X(2, 7, 3) X(3, 4, 1) X(3, 6, 1) X(3, 4, 3)
-
-// ... and the shapes that are also compiled with the other activation functions (CUDE_GENERAL_ACTS, cude_device.h)
-#define CUDE_CPEP_GENERAL_SHAPES(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2)
-
+// (the shape lists: cude_device.h CUDE_CPEP_SHAPES / CUDE_CPEP_GENERAL_SHAPES)
 // shapes with a kept-activation variant of the gradient kernel: the forward sweep must already hold the upper layers'
 // weights in VGPRs (Mlp::HAS_VW) and there must be an upper layer to keep
 template <class Net>

@@ -1019,13 +1019,11 @@ static hipError_t run_shape(int n_state, bool grad, const Cpep2Args& a, hipStrea
     return hipGetLastError();
 }
 
-#define CUDE_CPEP2_SHAPES(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2) X(2, 8, 2) X(2, 4, 3) X(2, 3, 2) X(2, 5, 2) X(2, 7, 2) X(3, 6, 2) X(2, 4, 1) X(2, 6, 1) X(2, 6, 3) X(2, 8, 1) X(2, 8, 3) X(3, 8, 2) X(2, 3, 1) X(2, 5, 1) X(2, 7, 1) X(2, 3, 3) X(2, 5, 3) X(2, 7, 3) X(3, 4, 1) X(3, 6, 1) X(3, 4, 3)
-
 bool cpep2_shape_supported(const NetShape& net, int n_state) {
     if (net.general() || net.generic()) return false;         // other activation functions / shapes: the one-lane kernels only
     if (n_state != 2 && n_state != 3) return false;
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return true;
-    CUDE_CPEP2_SHAPES(X)
+    CUDE_CPEP_SHAPES(X)
 #undef X
     return false;
 }
@@ -1041,7 +1039,7 @@ static int rev_occupancy() {
 }
 int cpep2_rev_waves_per_cu(const NetShape& net) {
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return rev_occupancy<NIN, W, D>();
-    CUDE_CPEP2_SHAPES(X)
+    CUDE_CPEP_SHAPES(X)
 #undef X
     return 0;
 }
@@ -1068,7 +1066,7 @@ hipError_t launch_cpep2_adjmap(const Cpep2Args& a, double* adj_map, hipStream_t 
 
 hipError_t launch_cpep2(const NetShape& net, int n_state, bool grad, const Cpep2Args& a, hipStream_t s) {
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return run_shape<NIN, W, D>(n_state, grad, a, s);
-    CUDE_CPEP2_SHAPES(X)
+    CUDE_CPEP_SHAPES(X)
 #undef X
     return hipErrorInvalidValue;
 }

@@ -1033,6 +1033,21 @@ inline bool general_acts_compiled(int hact, int oact) {
     return false;
 }
 
+// The network shapes the tuned kernels are compiled for: the ONE statement of each list, read by every dispatcher (a
+// shape is compiled for all launches of its model or for none).  Dispatchers test the shapes in the order listed.
+// c-peptide models, X(inputs, width, hidden layers) -- in three groups, because the longest translation units compile
+// one group each (cude_adaptive*.hip -DCUDE_AD_PART=k, cude_refine.hip -DCUDE_REFINE_PART=k)
+#define CUDE_CPEP_SHAPES_0(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2) X(2, 8, 2) X(2, 4, 3) X(2, 3, 2) X(2, 5, 2) X(2, 7, 2)
+#define CUDE_CPEP_SHAPES_1(X) X(3, 6, 2) X(2, 4, 1) X(2, 6, 1) X(2, 6, 3) X(2, 8, 1) X(2, 8, 3) X(3, 8, 2) X(2, 3, 1)
+#define CUDE_CPEP_SHAPES_2(X) X(2, 5, 1) X(2, 7, 1) X(2, 3, 3) X(2, 5, 3) X(2, 7, 3) X(3, 4, 1) X(3, 6, 1) X(3, 4, 3)
+#define CUDE_CPEP_SHAPES(X) CUDE_CPEP_SHAPES_0(X) CUDE_CPEP_SHAPES_1(X) CUDE_CPEP_SHAPES_2(X)
+// ... and those that are also compiled with the other activation functions (CUDE_GENERAL_ACTS)
+#define CUDE_CPEP_GENERAL_SHAPES(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2)
+// suppression model, X(width, hidden layers); with the other activation functions: the shapes of the reference's
+// experiment (stage-input mode only)
+#define CUDE_SUPP_SHAPES(X) X(3, 5) X(3, 2) X(4, 2) X(6, 2) X(5, 2) X(3, 3) X(8, 2) X(3, 4) X(4, 3) X(4, 4) X(5, 3) X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
+#define CUDE_SUPP_GENERAL_SHAPES(X) X(3, 5) X(3, 3)
+
 // ------------------------------------------------------------------------------------ analytic production
 // Drop-in for Mlp<2, W, D, 1> in the c-peptide kernel: the production term found by symbolic regression,
 //   production(dG, k) = dG >= 0 ? p0*dG/(dG + k) : 0,   p0 = 1.78 in the reference

@@ -767,6 +767,28 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
 
 using namespace cude::api;
 
+namespace {
+// Queues one tangent-linear solve of the context's model at `cond` on its stream: the per-subject SSE goes to `sse`, the
+// sums of `out` next to it, [sum SSE, failures] to c->partials.  keep_tape = false: an adaptive solve records no steps.
+hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, bool keep_tape) {
+    const auto fill = [&](auto& a) {
+        a.cond = cond; a.nn = c->nn.p; a.sse = sse; a.partials = c->partials.p;
+        if (!keep_tape) a.tape = nullptr;
+        a.out = out;
+    };
+    if (is_cpep(c)) {
+        cude::CpepSensArgs a{};
+        static_cast<cude::CpepArgs&>(a) = cpep_args(c);
+        fill(a);
+        return cude::launch_cpep_sens(c->net, c->cfg.n_state, a, c->stream);
+    }
+    cude::SuppSensArgs a{};
+    static_cast<cude::SuppArgs&>(a) = supp_args(c);
+    fill(a);
+    return cude::launch_supp_sens(c->net, a, c->stream);
+}
+}  // namespace
+
 extern "C" {
 
 int32_t cude_forward(cude_ctx* c, double* loss, double* per_subject_sse, double* traj) {
@@ -921,20 +943,7 @@ int32_t cude_sensitivity(cude_ctx* c, double* sens, double* info, double* score,
     out.sens = sens ? c->sens.p : nullptr;
     out.info = c->sens_info.p;
     out.score = c->sens_score.p;
-    hipError_t le;
-    if (cpep) {
-        cude::CpepSensArgs a{};
-        static_cast<cude::CpepArgs&>(a) = cpep_args(c);
-        a.cond = c->cond.p; a.nn = c->nn.p; a.sse = c->sse.p; a.partials = c->partials.p;
-        a.out = out;
-        le = cude::launch_cpep_sens(c->net, c->cfg.n_state, a, c->stream);
-    } else {
-        cude::SuppSensArgs a{};
-        static_cast<cude::SuppArgs&>(a) = supp_args(c);
-        a.cond = c->cond.p; a.nn = c->nn.p; a.sse = c->sse.p; a.partials = c->partials.p;
-        a.out = out;
-        le = cude::launch_supp_sens(c->net, a, c->stream);
-    }
+    const hipError_t le = launch_tangent(c, c->cond.p, c->sse.p, out, true);
     if (le == hipErrorInvalidValue) return fail(CUDE_ERR_UNSUPPORTED, "cude_sensitivity: no tangent kernel compiled for this network shape / model");
     HIP_TRY(le);
     if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
@@ -1395,19 +1404,7 @@ int32_t cude_refine_conditional(cude_ctx* c, const double* x0, double lower, dou
         out.info = info_t;
         out.score = score_t;
         for (int it = 0; it < max_evals && le == hipSuccess; it++) {
-            if (cpep) {
-                cude::CpepSensArgs a{};
-                static_cast<cude::CpepArgs&>(a) = cpep_args(c);
-                a.cond = r.xt; a.nn = c->nn.p; a.sse = sse_t; a.partials = c->partials.p; a.tape = nullptr;
-                a.out = out;
-                le = cude::launch_cpep_sens(c->net, c->cfg.n_state, a, c->stream);
-            } else {
-                cude::SuppSensArgs a{};
-                static_cast<cude::SuppArgs&>(a) = supp_args(c);
-                a.cond = r.xt; a.nn = c->nn.p; a.sse = sse_t; a.partials = c->partials.p; a.tape = nullptr;
-                a.out = out;
-                le = cude::launch_supp_sens(c->net, a, c->stream);
-            }
+            le = launch_tangent(c, r.xt, sse_t, out, false);
             if (le == hipSuccess) le = cude::launch_refine_step(1, k, r, c->stream);
         }
         // (adaptive mode: nothing of these solves is on the gradient's tape -- cude_adaptive_steps refuses afterwards)

@@ -11,9 +11,9 @@
 //
 // Two forms of one rule (refine_update below; the rule's text is in include/cude.h):
 //   * fused (fixed-step mode): one lane = one subject, one wave per workgroup; the lane keeps its subject's constants and
-//     the search state in registers, every evaluation walks the sweep of cpep_sens_kernel / supp_sens_kernel
-//     (cude_sens.hip; the same operations in the same order, without the trajectory stores) from a new first_layer_offset /
-//     cond_tangent, and the outer loop leaves when no lane of the wave is still running (ballot).  Lanes that have
+//     the search state in registers, every evaluation is one call of the sweep the sensitivity kernels call
+//     (cude_tangent.h cpep_tan_sweep / supp_tan_sweep, here without the trajectory stores) at the trial point, and the
+//     outer loop leaves when no lane of the wave is still running (ballot).  Lanes that have
 //     stopped run along masked: refine_update returns at once for them, their state stays what it was.  (The host adds
 //     one forward launch at the returned points, whose SSE is the one reported: cude_launch.hip.)
 //   * stepped (adaptive mode, or option "refine_fused" = 0): per evaluation one launch of the tangent solve at the trial
@@ -22,8 +22,7 @@
 // The file is compiled in parts (-DCUDE_REFINE_PART=k, as cude_sens.hip): 0 = the update kernel, the dispatchers, c-peptide
 // shape group 0 and the symbolic model; 1 = c-peptide group 1 and the general-activation shapes; 2 = c-peptide group 2;
 // 3 = the suppression model.
-#include "cude_adaptive.h"
-#include "cude_supp.h"
+#include "cude_tangent.h"
 
 namespace cude {
 
@@ -108,135 +107,23 @@ __device__ __forceinline__ void refine_store(const RefineArrays& r, int64_t i, c
 
 #if CUDE_REFINE_PART != 3
 // ---------------------------------------------------------------------------------- c-peptide models, fused
-// stages 2..7 of one Tsit5 step of  u' = A u + [f0 + q; 0]  (cude_sens.hip cpep_step_algebra)
-__device__ __forceinline__ void ref_step_algebra(double a11, double a12, double a21, double a22, double f0, double h,
-                                                 double y1, double y2, const double (&q)[7], double (&K)[7][2], double& Y1,
-                                                 double& Y2) {
-#pragma unroll
-    for (int st = 1; st < 7; st++) {
-        double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < st; j++) {
-            t1 = fma(Tab::a(st, j), K[j][0], t1);
-            t2 = fma(Tab::a(st, j), K[j][1], t2);
-        }
-        Y1 = fma(h, t1, y1);
-        Y2 = fma(h, t2, y2);
-        K[st][0] = fma(a11, Y1, fma(a12, Y2, f0 + q[st]));
-        K[st][1] = fma(a21, Y1, a22 * Y2);
-    }
-}
-
 // Net: Mlp<NIN, W, D, 1, false, false, HA, OA> or MmProd<RAW>.  The quadrature state of n_state = 3 enters no residual and
 // nothing here returns it: one kernel serves either n_state.
 template <class Net>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) void cpep_refine_kernel(CpepArgs a, RefineCfg k, RefineArrays r) {
-    constexpr int NC = Net::NC;
-    extern __shared__ double smem[];
-    double* s_q = smem;                         // [5][2][kBlock] stage forcings and their tangents
+    extern __shared__ double smem[];            // [5][2][kBlock] the sweep's stage forcings and their tangents
     const int lane = threadIdx.x;
     const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t i = active ? gid : a.N - 1;
-    const int64_t N = a.N;
-    cptr_t p = as_const(a.nn);
-    cptr_t phi = as_const(a.phi);
-    cptr_t obs_w = as_const(a.obs_w);
-    ciptr_t seg = as_const(a.seg);
-    ciptr_t obs_step = as_const(a.obs_step);
-    const int S = a.S, T = a.T;
-    const double h = a.h;
 
-    const double k0 = a.k0[i], k1 = a.k1[i], k2 = a.k2[i], c0 = a.c0[i];
-    const double a11 = -(k0 + k2), a12 = k1, a21 = k2, a22 = -k1, f0 = k0 * c0;
-    const double y20 = (k2 / k1) * c0;
-    const double K1a0 = fma(a11, c0, fma(a12, y20, f0)), K1b0 = fma(a21, c0, a22 * y20);
-    double cst[NC];
-    if (NC > 1) cst[1] = a.age[i];
-    const double pchk = NC > 1 ? fma(cst[1], 0.0, Net::param_check(p)) : Net::param_check(p);
-
+    const CpepTanConst kc = cpep_tan_load<Net>(a, i);
     RefineLane st;
     refine_start(st, k, r.x0[i], active);
 #pragma unroll 1
     while (__ballot(st.status == kRefineRunning) != 0ull) {
-        // ---- one evaluation at st.xt: the sweep of cpep_sens_kernel
-        cst[0] = Net::cond_input(st.xt);
-        double c[Net::NCST], dc[Net::NCST];
-        Net::first_layer_offset(p, cst, c);
-        Net::cond_tangent(p, cst[0], dc);
-        double y1 = c0, y2 = y20;
-        double s1 = 0.0, s2 = 0.0;
-        double qprev = 0.0, dqprev = 0.0;
-        double K1a = K1a0, K1b = K1b0, D1a = 0.0, D1b = 0.0;
-        int cur_seg = -1;
-        double g_lo = 0.0, g_d = 0.0;
-        double sse = 0.0, info = 0.0, score = 0.0, base = 0.0, dbase = 0.0;
-        double chk = fma(cst[0], 0.0, pchk);
-        int oi = 0, n = 0, s = -1;
-#pragma unroll 1
-        for (int e = -1; e < 5 * S; e++) {
-            double xv = 0.0;
-            if (e >= 0) {
-                const int sg = seg[e];
-                const double ph = phi[e];
-                if (sg != cur_seg) {
-                    cur_seg = sg;
-                    g_lo = a.dG[(int64_t)sg * N + i];
-                    g_d = a.dG[(int64_t)(sg + 1) * N + i] - g_lo;
-                    chk = fma(g_d, 0.0, fma(g_lo, 0.0, chk));
-                }
-                xv = fma(ph, g_d, g_lo);
-            }
-            const double x[1] = {xv}, dx[1] = {0.0};
-            double dv;
-            const double v = Net::template eval_jvp<false>(p, c, x, dc, dx, &dv);
-            if (e < 0) { base = v; dbase = dv; s = 0; continue; }
-            s_q[(2 * s) * kBlock + lane] = v - base;
-            s_q[(2 * s + 1) * kBlock + lane] = dv - dbase;
-            if (++s < 5) continue;
-            s = 0;
-            double q[7], dq[7];
-            q[0] = qprev;
-            dq[0] = dqprev;
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-                q[j + 1] = s_q[(2 * j) * kBlock + lane];
-                dq[j + 1] = s_q[(2 * j + 1) * kBlock + lane];
-            }
-            q[6] = q[5];
-            dq[6] = dq[5];
-            double K[7][2], DK[7][2];
-            K[0][0] = K1a; K[0][1] = K1b;
-            DK[0][0] = D1a; DK[0][1] = D1b;
-            double Y1 = y1, Y2 = y2, S1 = s1, S2 = s2;
-            ref_step_algebra(a11, a12, a21, a22, f0, h, y1, y2, q, K, Y1, Y2);
-            ref_step_algebra(a11, a12, a21, a22, 0.0, h, s1, s2, dq, DK, S1, S2);
-            while (oi < T && obs_step[oi] == n) {
-                double o1 = 0.0, d1 = 0.0;
-#pragma unroll
-                for (int j = 0; j < 7; j++) {
-                    const double w = obs_w[oi * 7 + j];
-                    o1 = fma(w, K[j][0], o1);
-                    d1 = fma(w, DK[j][0], d1);
-                }
-                o1 = fma(h, o1, y1);
-                d1 = fma(h, d1, s1);
-                const double rr = o1 - a.obs[(int64_t)oi * N + i];
-                sse = fma(rr, rr, sse);
-                info = fma(d1, d1, info);
-                score = fma(rr, d1, score);
-                oi++;
-            }
-            y1 = Y1; y2 = Y2;
-            s1 = S1; s2 = S2;
-            K1a = K[6][0]; K1b = K[6][1];
-            D1a = DK[6][0]; D1b = DK[6][1];
-            qprev = q[6];
-            dqprev = dq[6];
-            n++;
-        }
-        sse += chk;                                           // NaN iff an input of this subject is non-finite
-        refine_update(st, k, sse, score + chk, info + chk);
+        const TanSums e = cpep_tan_sweep<Net, 2>(a, kc, i, lane, st.xt, smem, TanNoStore());
+        refine_update(st, k, e.sse, e.score + e.chk, e.info + e.chk);
     }
     if (active) refine_store(r, i, st);
 }
@@ -288,7 +175,7 @@ hipError_t launch_cpep_refine(const NetShape& net, int n_state, const CpepArgs& 
         return a.cond_raw ? launch_cpep_fused<MmProd<true>>(n_state, a, k, r, s) : launch_cpep_fused<MmProd<false>>(n_state, a, k, r, s);
     if (net.general()) return launch_cpep_refine_part1(net, n_state, a, k, r, s);
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused<Mlp<NIN, W, D, 1>>(n_state, a, k, r, s);
-    CUDE_CPEP_AD_SHAPES_0(X)
+    CUDE_CPEP_SHAPES_0(X)
 #undef X
     const hipError_t e = launch_cpep_refine_part1(net, n_state, a, k, r, s);
     return e != hipErrorNotSupported ? e : launch_cpep_refine_part2(net, n_state, a, k, r, s);
@@ -307,12 +194,12 @@ static hipError_t launch_cpep_fused_general(const NetShape& net, int n_state, co
 hipError_t launch_cpep_refine_part1(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
     if (net.general()) {
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused_general<NIN, W, D>(net, n_state, a, k, r, s);
-        X(2, 4, 2) X(2, 6, 2) X(3, 4, 2)
+        CUDE_CPEP_GENERAL_SHAPES(X)
 #undef X
         return hipErrorInvalidValue;
     }
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused<Mlp<NIN, W, D, 1>>(n_state, a, k, r, s);
-    CUDE_CPEP_AD_SHAPES_1(X)
+    CUDE_CPEP_SHAPES_1(X)
 #undef X
     return hipErrorNotSupported;
 }
@@ -320,7 +207,7 @@ hipError_t launch_cpep_refine_part1(const NetShape& net, int n_state, const Cpep
 #elif CUDE_REFINE_PART == 2
 hipError_t launch_cpep_refine_part2(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
 #define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused<Mlp<NIN, W, D, 1>>(n_state, a, k, r, s);
-    CUDE_CPEP_AD_SHAPES_2(X)
+    CUDE_CPEP_SHAPES_2(X)
 #undef X
     return hipErrorInvalidValue;
 }
@@ -330,107 +217,20 @@ hipError_t launch_cpep_refine_part2(const NetShape& net, int n_state, const Cpep
 template <int W, int D, int HA, int OA>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) void supp_refine_kernel(SuppArgs a, RefineCfg k, RefineArrays r) {
     using Net = Mlp<4, W, D, 3, false, false, HA, OA>;
-    extern __shared__ double smem[];
-    double* s_K = smem;                  // [7][4] stage derivatives of (u2, u3, du2, du3)
+    extern __shared__ double smem[];            // [7][4][kBlock] the sweep's stage derivatives
     const int lane = threadIdx.x;
     const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t i = active ? gid : a.N - 1;
-    const int64_t N = a.N;
-    cptr_t p = as_const(a.nn);
-    cptr_t obs_w = as_const(a.obs_w);
-    cptr_t rho = as_const(a.rho);
-    cptr_t obs_rho = as_const(a.obs_rho);
-    ciptr_t obs_step = as_const(a.obs_step);
-    const int S = a.S, T = a.T;
-    const double h = a.h;
-#define KROW(j, s) s_K[((j) * 4 + (s)) * kBlock + lane]
 
-    const double u10 = a.data[((int64_t)0 * T + 0) * N + i];     // u1(t_0): every later u1 is this times a table entry
-    const double u20 = a.data[((int64_t)1 * T + 0) * N + i], u30 = a.data[((int64_t)2 * T + 0) * N + i];
-    const double pchk = fma(u10 + u20 + u30, 0.0, Net::param_check(p));
-
+    const SuppTanConst kc = supp_tan_load<Net>(a, i);
     RefineLane rs;
     refine_start(rs, k, r.x0[i], active);
 #pragma unroll 1
     while (__ballot(rs.status == kRefineRunning) != 0ull) {
-        // ---- one evaluation at rs.xt: the sweep of supp_sens_kernel
-        const double cst0 = exp(rs.xt);
-        const double cst[1] = {cst0};
-        double c[W], dc[W];
-        Net::first_layer_offset(p, cst, c);
-        Net::cond_tangent(p, cst0, dc);
-#pragma unroll
-        for (int j = 0; j < 7; j++)
-#pragma unroll
-            for (int s = 0; s < 4; s++) KROW(j, s) = 0.0;     // (a rejected trial may have left NaN in this lane's rows)
-        double y[4] = {u20, u30, 0.0, 0.0};
-        double sse = fma(cst0, 0.0, pchk);                    // NaN iff an input of this subject is non-finite
-        double info = 0.0, score = 0.0;
-        int oi = 0, n = 0, st = 0;
-#pragma unroll 1
-        for (int e = 0; e <= 6 * S; e++) {
-            double u[4];
-            const double u1 = u10 * rho[e];
-            if (st == 0) {
-#pragma unroll
-                for (int s = 0; s < 4; s++) u[s] = y[s];
-            } else {
-                double t[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int j = 0; j < 6; j++) {
-                    const double aj = TS_A[st][j];
-#pragma unroll
-                    for (int s = 0; s < 4; s++) t[s] = fma(aj, KROW(j, s), t[s]);
-                }
-#pragma unroll
-                for (int s = 0; s < 4; s++) u[s] = fma(h, t[s], y[s]);
-            }
-            double du[4];
-            {
-                const double x[3] = {u1, u[0], u[1]}, dx[3] = {0.0, u[2], u[3]};
-                double duh;
-                const double uh = Net::template eval_jvp<true>(p, c, x, dc, dx, &duh);
-                du[0] = fma(0.4, u1, -uh);
-                du[1] = fma(-0.3, u[1], uh);
-                du[2] = -duh;
-                du[3] = fma(-0.3, u[3], duh);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; s++) KROW(st, s) = du[s];
-            if (e == 0) { st = 1; continue; }
-            if (st < 6) { st++; continue; }
-            while (oi < T && obs_step[oi] == n) {
-                double o[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-                for (int j = 0; j < 7; j++) {
-                    const double w = obs_w[oi * 7 + j];
-#pragma unroll
-                    for (int s = 0; s < 4; s++) o[s] = fma(w, KROW(j, s), o[s]);
-                }
-#pragma unroll
-                for (int s = 0; s < 4; s++) o[s] = fma(h, o[s], y[s]);
-                {
-                    const double rr = u10 * obs_rho[oi] - a.data[((int64_t)0 * T + oi) * N + i];
-                    sse = fma(rr * a.iscale2[0], rr, sse);
-                }
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    const double rr = o[s] - a.data[((int64_t)(s + 1) * T + oi) * N + i];
-                    sse = fma(rr * a.iscale2[s + 1], rr, sse);
-                    info = fma(o[2 + s] * a.iscale2[s + 1], o[2 + s], info);
-                    score = fma(rr * a.iscale2[s + 1], o[2 + s], score);
-                }
-                oi++;
-            }
-#pragma unroll
-            for (int s = 0; s < 4; s++) { y[s] = u[s]; KROW(0, s) = du[s]; }
-            st = 1;
-            n++;
-        }
-        refine_update(rs, k, sse, score, info);
+        const TanSums e = supp_tan_sweep<Net>(a, kc, i, lane, rs.xt, smem, TanNoStore());
+        refine_update(rs, k, e.sse, e.score, e.info);
     }
-#undef KROW
     if (active) refine_store(r, i, rs);
 }
 

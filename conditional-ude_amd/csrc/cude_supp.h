@@ -10,9 +10,4 @@ struct SuppNetSel { using type = SuppNetG<W, D, HA, OA>; };
 template <int W, int D>
 struct SuppNetSel<W, D, kActHiddenTanh, kActOutSoftplus> { using type = SuppNet<W, D>; };
 
-// the shape of the reference's experiment with the other activation functions (stage-input mode only)
-#define CUDE_SUPP_GENERAL_SHAPES(X) X(3, 5) X(3, 3)
-
-#define CUDE_SUPP_SHAPES(X) X(3, 5) X(3, 2) X(4, 2) X(6, 2) X(5, 2) X(3, 3) X(8, 2) X(3, 4) X(4, 3) X(4, 4) X(5, 3) X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
-
 }  // namespace cude

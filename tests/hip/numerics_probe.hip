@@ -231,25 +231,20 @@ hipError_t run_param_check(const double* p, int n_sets, double* out) {
     return hipSuccess;
 }
 
-// the networks the product kernels are compiled for (csrc/cude_cpep.hip CUDE_CPEP_SHAPES, csrc/cude_supp.h
-// CUDE_SUPP_SHAPES; CUDE_CPEP_GENERAL_SHAPES / CUDE_SUPP_GENERAL_SHAPES x CUDE_GENERAL_ACTS, one shape per pair)
+// the networks the product kernels are compiled for (csrc/cude_device.h CUDE_CPEP_SHAPES, CUDE_SUPP_SHAPES;
+// CUDE_CPEP_GENERAL_SHAPES / CUDE_SUPP_GENERAL_SHAPES x CUDE_GENERAL_ACTS, one shape per pair)
 enum Family { kCpep = 0, kSupp = 1, kCpepG = 2, kSuppG = 3 };
-#define PROBE_CPEP_SHAPES(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2) X(2, 8, 2) X(2, 4, 3) X(2, 3, 2) X(2, 5, 2) X(2, 7, 2) \
-    X(3, 6, 2) X(2, 4, 1) X(2, 6, 1) X(2, 6, 3) X(2, 8, 1) X(2, 8, 3) X(3, 8, 2) X(2, 3, 1) X(2, 5, 1) X(2, 7, 1)       \
-    X(2, 3, 3) X(2, 5, 3) X(2, 7, 3) X(3, 4, 1) X(3, 6, 1) X(3, 4, 3)
-#define PROBE_SUPP_SHAPES(X) X(3, 5) X(3, 2) X(4, 2) X(6, 2) X(5, 2) X(3, 3) X(8, 2) X(3, 4) X(4, 3) X(4, 4) X(5, 3) \
-    X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
 
 // calls F<Net, NIN>::run(args...) for the network (family, nin, w, d, ha, oa); hipErrorInvalidValue if it is not compiled
 template <template <class, int> class F, class... Args>
 hipError_t dispatch(int family, int nin, int w, int dd, int ha, int oa, Args... args) {
 #define C1(NIN, W, D) \
     if (family == kCpep && nin == NIN && w == W && dd == D && ha == 0 && oa == 0) return F<CpepNet<NIN, W, D>, NIN>::run(args...);
-    PROBE_CPEP_SHAPES(C1)
+    CUDE_CPEP_SHAPES(C1)
 #undef C1
 #define S1(W, D) \
     if (family == kSupp && nin == 4 && w == W && dd == D && ha == 0 && oa == 0) return F<SuppNet<W, D>, 4>::run(args...);
-    PROBE_SUPP_SHAPES(S1)
+    CUDE_SUPP_SHAPES(S1)
 #undef S1
 #define G1(HA, OA)                                                                            \
     if (family == kCpepG && nin == 2 && w == 4 && dd == 2 && ha == HA && oa == OA)            \

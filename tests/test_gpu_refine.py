@@ -190,6 +190,8 @@ def test_same_minimiser_as_the_search_on_unique_basins(name):
 # ----------------------------------------------------------------------------- 4. stepped form = fused form
 @pytest.mark.parametrize("name", ["cpep-2661-ns3", "sym-raw", "supp-4355"])
 def test_stepped_form_equals_fused_form(name):
+    """The stepped form runs the sensitivity kernels, the fused form the fit kernels: a fork of the sweep they share, or of
+    the rule, shows here as a differing bit."""
     out = []
     N, box, x_const, max_step = CASES[name][3], CASES[name][4], CASES[name][5], CASES[name][6]
     for fused in (1, 0):
@@ -201,7 +203,8 @@ def test_stepped_form_equals_fused_form(name):
     a, b = out
     dx = np.abs(a["x"] - b["x"]) / (1 + np.abs(a["x"]))
     print(f"{name}: max |dx|/(1+|x|) {dx.max():.2e}, evals differ for {np.count_nonzero(a['evals'] != b['evals'])}")
-    assert np.array_equal(a["status"], b["status"]) and np.all(dx <= X_BAR)
+    # bit for bit: both forms evaluate through the one sweep of csrc/cude_tangent.h and judge by the one refine_update
+    assert np.array_equal(a["x"], b["x"]) and np.array_equal(a["evals"], b["evals"]) and np.array_equal(a["status"], b["status"])
 
 
 # ----------------------------------------------------------------------------- 5. adaptive mode
