@@ -140,6 +140,40 @@ cude::Cpep2Args chunk_args(cude_ctx* c, const cude::CpepArgs& base, bool all_blo
     return a2;
 }
 
+// chunks of a forward-only time-split launch: the forward-only split where there is one, otherwise the gradient's
+int forward_chunks(const cude_ctx* c) { return c->chunks_f > 1 ? c->chunks_f : c->chunks; }
+
+// Kernel timing: a pair of events from the context's pool (grown on demand), the first one recorded on the stream; the
+// caller records *e1 behind what it times.  WHICH launches are timed is the caller's rule.
+int32_t timed_pair(cude_ctx* c, hipEvent_t* e0, hipEvent_t* e1) {
+    if (c->ev_used == c->ev_pool.size()) {
+        hipEvent_t a, b;
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        c->ev_pool.emplace_back(a, b);
+    }
+    *e0 = c->ev_pool[c->ev_used].first;
+    *e1 = c->ev_pool[c->ev_used].second;
+    c->ev_used++;
+    HIP_TRY(hipEventRecord(*e0, c->stream));
+    return CUDE_OK;
+}
+
+// Tail of a time-split gradient launch in one launch (launch_chunked_tail): the network gradient over the reverse chunks'
+// rows `partials2`, the loss / failure columns over the scan's rows `partials`, and the chunks' shares `g_cond_part` of
+// the conditional gradient summed into g_cond (set k at g_cond + k * g_cond_set_stride).  The caller adds what only a
+// single-set evaluation has (state advance, page-locked pair, exchange).
+cude::ChunkedTailArgs chunked_tail_args(const cude_ctx* c, const double* partials2, const double* partials, double* out,
+                                        const double* g_cond_part, double* g_cond, int64_t g_cond_set_stride) {
+    cude::ChunkedTailArgs ta{};
+    ta.partials2 = partials2; ta.rows2 = c->nblocks * c->chunks;
+    ta.partials = partials; ta.rows = c->nblocks;
+    ta.P = c->P; ta.out = out; ta.out_stride = c->P + 2;
+    ta.mask = c->param_mask.p; ta.n_mask = c->P;
+    ta.g_cond_part = g_cond_part; ta.L = c->chunks; ta.N = c->N; ta.g_cond = g_cond; ta.g_cond_set_stride = g_cond_set_stride;
+    return ta;
+}
+
 }  // namespace
 
 // Relative cost of one gradient launch when `waves` workgroups of `evals` network evaluations each run on `slots`
@@ -362,16 +396,8 @@ int32_t run_ensemble(cude_ctx* c, bool grad, double* traj_dev, bool local_only, 
     bool fused_final = false;
     c->loss_in_pinned = false;
     if (c->timing && !c->capturing && (c->timing_count++ % c->timing_period) == 0) {
-        if (c->ev_used == c->ev_pool.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            c->ev_pool.emplace_back(a, b);
-        }
-        e0 = c->ev_pool[c->ev_used].first;
-        e1 = c->ev_pool[c->ev_used].second;
-        c->ev_used++;
-        HIP_TRY(hipEventRecord(e0, c->stream));
+        int32_t rc = timed_pair(c, &e0, &e1);
+        if (rc) return rc;
     }
     if (is_cpep(c)) {
         cude::CpepArgs a = cpep_args(c);
@@ -483,15 +509,11 @@ int32_t run_ensemble(cude_ctx* c, bool grad, double* traj_dev, bool local_only, 
     } else if (grad && is_cpep(c) && c->chunks > 1 && c->opt.fused_tail) {
         // one launch: the network gradient over the reverse chunks' rows, the loss / failure columns over the scan's rows
         // (+ state advance, page-locked pair, exchange) and the chunks' shares of the conditional gradient
-        cude::ChunkedTailArgs ta{};
-        ta.partials2 = c->partials2.p; ta.rows2 = c->nblocks * c->chunks;
-        ta.partials = c->partials.p; ta.rows = c->nblocks;
-        ta.P = P; ta.out = c->g_nn.p; ta.out_stride = P + 2;
-        ta.mask = c->param_mask.p; ta.n_mask = P;
+        cude::ChunkedTailArgs ta =
+            chunked_tail_args(c, c->partials2.p, c->partials.p, c->g_nn.p, c->g_cond_part.p, c->g_cond.p, c->N);
         if (adv_red) ta.adv = *adv_red;
         ta.host_tail = host_tail;
         if (xq) ta.xchg = *xq;
-        ta.g_cond_part = c->g_cond_part.p; ta.L = c->chunks; ta.N = c->N; ta.g_cond = c->g_cond.p; ta.g_cond_set_stride = c->N;
         HIP_TRY(cude::launch_chunked_tail(ta, 1, c->stream));
     } else if (grad && is_cpep(c) && c->chunks > 1) {
         HIP_TRY(cude::launch_reduce_cols(c->partials2.p, c->nblocks * c->chunks, P, 0, P, c->g_nn.p, c->stream, 1,
@@ -724,10 +746,8 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
             HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, true, a2, c->stream));
             // network gradient: the reverse chunks' partial rows; loss / failure columns: the scan's
             if (c->opt.fused_tail) {
-                cude::ChunkedTailArgs ta{};
-                ta.partials2 = c->ms_p2.p; ta.rows2 = nb * L; ta.partials = c->ms_part.p; ta.rows = nb;
-                ta.P = P; ta.out = out_k; ta.out_stride = P + 2; ta.mask = c->param_mask.p; ta.n_mask = P;
-                ta.g_cond_part = c->ms_gcp.p; ta.L = L; ta.N = N; ta.g_cond = g_cond_k; ta.g_cond_set_stride = stride_cond;
+                const cude::ChunkedTailArgs ta =
+                    chunked_tail_args(c, c->ms_p2.p, c->ms_part.p, out_k, c->ms_gcp.p, g_cond_k, stride_cond);
                 HIP_TRY(cude::launch_chunked_tail(ta, (int)kn, c->stream));
             } else {
                 HIP_TRY(cude::launch_reduce_cols(c->ms_p2.p, nb * L, P, 0, P, out_k, c->stream, (int)kn, c->param_mask.p, P, P + 2));
@@ -786,6 +806,65 @@ hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cu
     static_cast<cude::SuppArgs&>(a) = supp_args(c);
     fill(a);
     return cude::launch_supp_sens(c->net, a, c->stream);
+}
+
+// A forward solve of n_sets parameter sets in one launch (set k: nn + k * stride_nn, cond + k * N; the set index is a grid
+// dimension): what the entry points that batch solves differ in.  The rest of the launch is forward_sets's.
+struct SetsForward {
+    const double* cond = nullptr;       // [n_sets][N]
+    const double* nn = nullptr;         // stride_nn = 0: one network for every set
+    int64_t stride_nn = 0;
+    int n_sets = 0;
+    double* sse = nullptr;              // [n_sets][N] per-subject SSE, or null
+    double* partials = nullptr;         // [n_sets][nblocks][P + 2] of a launch that is not split: [sum SSE, failures] in
+                                        // the last two columns (reserve_sets_forward)
+    bool split = false;                 // the time-split forward kernels (c-peptide models, fixed step, chunks > 1)
+    const cude::MhSpecArgs* resolve_in_scan = nullptr;      // split only: the scan launch resolves this speculative round
+};
+
+// Scratch of forward_sets for up to max_sets sets per launch.  A split launch works in the context's own (ms_fsum: every
+// set's forced chunk responses, ms_part: kept between calls), any other in the caller's `own_part`, which goes into
+// SetsForward::partials.  Never under stream capture (no entry point that batches solves runs there).
+int32_t reserve_sets_forward(cude_ctx* c, int64_t max_sets, bool split, DevBuf<double>& own_part) {
+    const size_t part = (size_t)max_sets * c->nblocks * (c->P + 2);
+    if (!split) {
+        HIP_TRY(own_part.resize(part));
+        return CUDE_OK;
+    }
+    HIP_TRY(c->ms_fsum.reserve((size_t)max_sets * forward_chunks(c) * (3 + c->T) * c->N));
+    HIP_TRY(c->ms_part.reserve(part));
+    return CUDE_OK;
+}
+
+// Queues the launch on the context's stream; no synchronisation.
+int32_t forward_sets(cude_ctx* c, const SetsForward& s) {
+    const auto fill = [&](auto& a) {
+        a.cond = s.cond; a.nn = s.nn; a.sse = s.sse;
+        a.partials = s.split ? c->ms_part.p : s.partials;
+        a.n_sets = s.n_sets; a.set_stride_nn = s.stride_nn; a.set_stride_cond = c->N;
+    };
+    if (!is_cpep(c)) {
+        cude::SuppArgs a = supp_args(c);
+        fill(a);
+        HIP_TRY(cude::launch_supp(c->net, false, a, c->stream));
+    } else {
+        cude::CpepArgs a = cpep_args(c);
+        fill(a);
+        if (s.split) {
+            cude::Cpep2Args a2 = chunk_args(c, a, /*all_blocks=*/true, /*forward_only=*/true);
+            a2.fsum = c->ms_fsum.p;
+            if (s.resolve_in_scan) {
+                a2.spec_slots = 1 << s.resolve_in_scan->depth_resolve;
+                a2.spec = *s.resolve_in_scan;
+            }
+            HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, false, a2, c->stream));
+        } else {
+            HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
+        }
+    }
+    // (adaptive launches leave the accepted-step counts of set 0 behind, and overwrite those a gradient's tape went with)
+    if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
+    return CUDE_OK;
 }
 }  // namespace
 
@@ -980,28 +1059,18 @@ int32_t cude_multistart_forward(cude_ctx* c, int32_t n_sets, const double* nn_se
     DevBuf<double> d_nn, d_cond, d_part, d_out;
     HIP_TRY(d_nn.resize((size_t)chunk * P));
     HIP_TRY(d_cond.resize((size_t)chunk * N));
-    HIP_TRY(d_part.resize((size_t)chunk * nb * (P + 2)));
+    if ((rc = reserve_sets_forward(c, chunk, false, d_part))) return rc;
     HIP_TRY(d_out.resize((size_t)chunk * 2));
     std::vector<double> h_out((size_t)chunk * 2);
     double reg = 0.0;
+    SetsForward fwd;                                      // (network, conditional parameters) pairs
+    fwd.cond = d_cond.p; fwd.nn = d_nn.p; fwd.stride_nn = P; fwd.partials = d_part.p;
     for (int64_t k0 = 0; k0 < n_sets; k0 += chunk) {
         const int64_t kn = std::min<int64_t>(chunk, n_sets - k0);
         HIP_TRY(hipMemcpyAsync(d_nn.p, nn_sets + k0 * P, kn * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(d_cond.p, cond_sets + k0 * N, kn * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (is_cpep(c)) {
-            cude::CpepArgs a = cpep_args(c);
-            a.cond = d_cond.p; a.nn = d_nn.p;
-            a.partials = d_part.p;
-            a.n_sets = (int32_t)kn; a.set_stride_nn = P; a.set_stride_cond = N;
-            HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
-        } else {
-            cude::SuppArgs a = supp_args(c);
-            a.cond = d_cond.p; a.nn = d_nn.p;
-            a.partials = d_part.p;
-            a.n_sets = (int32_t)kn; a.set_stride_nn = P; a.set_stride_cond = N;
-            HIP_TRY(cude::launch_supp(c->net, false, a, c->stream));
-        }
-        if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
+        fwd.n_sets = (int)kn;
+        if ((rc = forward_sets(c, fwd))) return rc;
         HIP_TRY(cude::launch_reduce_sets(d_part.p, (int)kn, nb, P + 2, P, d_out.p, c->stream));
         if (distributed(c) && (rc = allreduce_dev(c, d_out.p, (size_t)kn * 2))) return rc;
         HIP_TRY(hipMemcpyAsync(h_out.data(), d_out.p, kn * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1040,7 +1109,7 @@ int32_t cude_screen_candidates(cude_ctx* c, int64_t n_candidates, int32_t n_keep
     DevBuf<int> d_sel;
     HIP_TRY(d_nn.resize((size_t)chunk * P));
     HIP_TRY(d_cond.resize((size_t)chunk * N));
-    HIP_TRY(d_part.resize((size_t)chunk * nb * (P + 2)));
+    if ((rc = reserve_sets_forward(c, chunk, false, d_part))) return rc;
     HIP_TRY(d_sums.resize((size_t)chunk * 2));
     HIP_TRY(d_loss.resize((size_t)chunk));
     HIP_TRY(d_work.resize((size_t)chunk + n_keep));
@@ -1053,26 +1122,16 @@ int32_t cude_screen_candidates(cude_ctx* c, int64_t n_candidates, int32_t n_keep
     }
     std::vector<double> h_nn((size_t)chunk * P), h_cond((size_t)chunk * N);
     int have = 0, cur = 0;
+    SetsForward fwd;                                      // (network, conditional parameters) pairs
+    fwd.cond = d_cond.p; fwd.nn = d_nn.p; fwd.stride_nn = P; fwd.partials = d_part.p;
     for (int64_t k0 = 0; k0 < n_candidates; k0 += chunk) {
         const int64_t kn = std::min<int64_t>(chunk, n_candidates - k0);
         if (gen(k0, (int32_t)kn, h_nn.data(), h_cond.data(), user) < 0)
             return fail(CUDE_ERR_ARG, "candidate generator reported an error");
         HIP_TRY(hipMemcpyAsync(d_nn.p, h_nn.data(), kn * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(d_cond.p, h_cond.data(), kn * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (is_cpep(c)) {
-            cude::CpepArgs a = cpep_args(c);
-            a.cond = d_cond.p; a.nn = d_nn.p;
-            a.partials = d_part.p;
-            a.n_sets = (int32_t)kn; a.set_stride_nn = P; a.set_stride_cond = N;
-            HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
-        } else {
-            cude::SuppArgs a = supp_args(c);
-            a.cond = d_cond.p; a.nn = d_nn.p;
-            a.partials = d_part.p;
-            a.n_sets = (int32_t)kn; a.set_stride_nn = P; a.set_stride_cond = N;
-            HIP_TRY(cude::launch_supp(c->net, false, a, c->stream));
-        }
-        if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
+        fwd.n_sets = (int)kn;
+        if ((rc = forward_sets(c, fwd))) return rc;
         HIP_TRY(cude::launch_reduce_sets(d_part.p, (int)kn, nb, P + 2, P, d_sums.p, c->stream));
         if (distributed(c) && (rc = allreduce_dev(c, d_sums.p, (size_t)kn * 2))) return rc;
         HIP_TRY(cude::launch_set_losses((int)kn, d_sums.p, d_nn.p, P, c->cfg.lambda, c->n_global, d_loss.p, c->stream));
@@ -1186,25 +1245,15 @@ int32_t cude_profile_conditional(cude_ctx* c, int32_t n_points, const double* va
     HIP_TRY(d_val.resize((size_t)chunk));
     HIP_TRY(d_cond.resize((size_t)chunk * N));
     HIP_TRY(d_sse.resize((size_t)chunk * N));
-    HIP_TRY(d_part.resize((size_t)chunk * nb * (P + 2)));
+    if ((rc = reserve_sets_forward(c, chunk, false, d_part))) return rc;
+    SetsForward fwd;                                      // one network, kn grid values
+    fwd.cond = d_cond.p; fwd.nn = c->nn.p; fwd.sse = d_sse.p; fwd.partials = d_part.p;
     for (int64_t k0 = 0; k0 < n_points; k0 += chunk) {
         const int64_t kn = std::min<int64_t>(chunk, n_points - k0);
         HIP_TRY(hipMemcpyAsync(d_val.p, values + k0, kn * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(cude::launch_fill_rows(N, (int)kn, d_val.p, d_cond.p, c->stream));
-        if (is_cpep(c)) {
-            cude::CpepArgs a = cpep_args(c);
-            a.cond = d_cond.p; a.nn = c->nn.p;
-            a.sse = d_sse.p; a.partials = d_part.p;
-            a.n_sets = (int32_t)kn; a.set_stride_nn = 0; a.set_stride_cond = N;      // one network, kn grid values
-            HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
-        } else {
-            cude::SuppArgs a = supp_args(c);
-            a.cond = d_cond.p; a.nn = c->nn.p;
-            a.sse = d_sse.p; a.partials = d_part.p;
-            a.n_sets = (int32_t)kn; a.set_stride_nn = 0; a.set_stride_cond = N;
-            HIP_TRY(cude::launch_supp(c->net, false, a, c->stream));
-        }
-        if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
+        fwd.n_sets = (int)kn;
+        if ((rc = forward_sets(c, fwd))) return rc;
         HIP_TRY(hipMemcpyAsync(sse_out + k0 * N, d_sse.p, kn * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -1243,62 +1292,36 @@ int32_t cude_fit_conditional(cude_ctx* c, double lower, double upper, int32_t n_
     int fdepth = c->opt.fit_spec;
     const bool fsplit = is_cpep(c) && !adaptive(c) && c->chunks > 1;
     if (fdepth < 0) {
-        const int64_t waves1 = c->nblocks * (fsplit ? (c->chunks_f > 1 ? c->chunks_f : c->chunks) : 1);
+        const int64_t waves1 = c->nblocks * (fsplit ? forward_chunks(c) : 1);
         const int64_t room = fsplit ? 4096 : 1024;
         fdepth = 30 * waves1 <= room ? 4 : (14 * waves1 <= room ? 3 : (6 * waves1 <= room ? 2 : 1));
     }
     if (c->net.generic()) fdepth = 0;
     fdepth = std::min(fdepth, (int)cude::kFitSpecMaxDepth);
+    DevBuf<double> d_cand, d_sse, d_part, d_vals;          // (several probes per launch; alive until the final copies are in)
     if (fdepth >= 1) {
         const int P = c->P;
         const int64_t nb = c->nblocks;
-        const int Lf = fsplit ? (c->chunks_f > 1 ? c->chunks_f : c->chunks) : 1;
         // sets per launch: the tree's, and for the grid scan as many as ~256 MB of per-set scratch allow
         const int tree_sets = 2 * ((1 << fdepth) - 1);
-        const double per_set = 8.0 * ((double)N * (2 + (fsplit ? (double)Lf * (3 + c->T) : 0.0)) + (double)nb * (P + 2));
+        const double per_set =
+            8.0 * ((double)N * (2 + (fsplit ? (double)forward_chunks(c) * (3 + c->T) : 0.0)) + (double)nb * (P + 2));
         const int grid_sets = (int)std::max<int64_t>(1, std::min<int64_t>(n_grid, (int64_t)(256e6 / per_set)));
         const int max_sets = std::max(tree_sets, grid_sets);
-        DevBuf<double> d_cand, d_sse, d_part, d_vals;
         HIP_TRY(d_cand.resize((size_t)max_sets * N));
         HIP_TRY(d_sse.resize((size_t)max_sets * N));
         HIP_TRY(d_vals.resize((size_t)n_grid));
-        if (fsplit) {
-            HIP_TRY(c->ms_fsum.reserve((size_t)max_sets * Lf * (3 + c->T) * N));
-            HIP_TRY(c->ms_part.reserve((size_t)max_sets * nb * (P + 2)));
-        } else {
-            HIP_TRY(d_part.resize((size_t)max_sets * nb * (P + 2)));
-        }
-        auto solve_sets = [&](int n_sets) -> int32_t {           // SSE of every subject at cand[set][subject]
-            if (is_cpep(c)) {
-                cude::CpepArgs a = cpep_args(c);
-                a.cond = d_cand.p; a.nn = c->nn.p; a.sse = d_sse.p; a.traj = nullptr; a.auc = nullptr;
-                a.g_cond = c->g_cond.p; a.partials = fsplit ? c->ms_part.p : d_part.p;
-                a.n_sets = n_sets; a.set_stride_nn = 0; a.set_stride_cond = N;
-                if (fsplit) {
-                    cude::Cpep2Args a2 = chunk_args(c, a, /*all_blocks=*/true, /*forward_only=*/true);
-                    a2.fsum = c->ms_fsum.p;
-                    HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, false, a2, c->stream));
-                } else {
-                    HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
-                }
-            } else {
-                cude::SuppArgs a = supp_args(c);
-                a.cond = d_cand.p; a.nn = c->nn.p; a.sse = d_sse.p; a.traj = nullptr;
-                a.g_cond = c->g_cond.p; a.partials = d_part.p;
-                a.n_sets = n_sets; a.set_stride_nn = 0; a.set_stride_cond = N;
-                HIP_TRY(cude::launch_supp(c->net, false, a, c->stream));
-            }
-            if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
-            return CUDE_OK;
-        };
+        if ((rc = reserve_sets_forward(c, max_sets, fsplit, d_part))) return rc;
+        SetsForward fwd;                                      // SSE of every subject at cand[set][subject], one network
+        fwd.cond = d_cand.p; fwd.nn = c->nn.p; fwd.sse = d_sse.p; fwd.partials = d_part.p; fwd.split = fsplit;
         std::vector<double> vals((size_t)n_grid);
         for (int k = 0; k < n_grid; k++) vals[k] = (k == n_grid - 1) ? upper : std::fma((double)k, f.step, lower);
         HIP_TRY(hipMemcpyAsync(d_vals.p, vals.data(), (size_t)n_grid * sizeof(double), hipMemcpyHostToDevice, c->stream));
         for (int k0 = 0; k0 < n_grid; k0 += grid_sets) {      // coarse scan of the box
-            const int kn = std::min(grid_sets, n_grid - k0);
-            HIP_TRY(cude::launch_fill_rows(N, kn, d_vals.p + k0, d_cand.p, c->stream));
-            if ((rc = solve_sets(kn))) return rc;
-            HIP_TRY(cude::launch_fit_grid_all(f, k0, kn, d_vals.p, d_sse.p, c->stream));
+            fwd.n_sets = std::min(grid_sets, n_grid - k0);
+            HIP_TRY(cude::launch_fill_rows(N, fwd.n_sets, d_vals.p + k0, d_cand.p, c->stream));
+            if ((rc = forward_sets(c, fwd))) return rc;
+            HIP_TRY(cude::launch_fit_grid_all(f, k0, fwd.n_sets, d_vals.p, d_sse.p, c->stream));
             if (k0 == 0 && (rc = maybe_regroup(c))) return rc; // (adaptive mode: the first launch has told the step counts)
         }
         HIP_TRY(hipStreamSynchronize(c->stream));             // vals (host vector) was read by the copy above
@@ -1306,31 +1329,26 @@ int32_t cude_fit_conditional(cude_ctx* c, double lower, double upper, int32_t n_
         for (int it = 0; it < n_iters;) {                     // golden section inside the bracket, d steps per launch
             const int d = std::min(fdepth, n_iters - it);
             HIP_TRY(cude::launch_fit_tree(f, d, 0, 0, d_cand.p, d_sse.p, c->stream));
-            if ((rc = solve_sets(2 * ((1 << d) - 1)))) return rc;
+            fwd.n_sets = 2 * ((1 << d) - 1);
+            if ((rc = forward_sets(c, fwd))) return rc;
             it += d;
             HIP_TRY(cude::launch_fit_tree(f, d, 1, it == n_iters ? 1 : 0, d_cand.p, d_sse.p, c->stream));
         }
-        if ((rc = run_ensemble(c, false, nullptr, true, f.c, sse_c))) return rc;       // at the returned midpoint
-        HIP_TRY(cude::launch_fit(3, f, 0, 0.0, c->stream));
-        HIP_TRY(hipMemcpyAsync(cond_out, f.c, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (objective_out) HIP_TRY(hipMemcpyAsync(objective_out, f.fc, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (sse_out) HIP_TRY(hipMemcpyAsync(sse_out, sse_c, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return CUDE_OK;
-    }
-    // everything below is queued on the stream; the only synchronisation is the copy-back at the end
-    for (int k = 0; k < n_grid; k++) {                    // coarse scan of the box
-        const double x = (k == n_grid - 1) ? upper : std::fma((double)k, f.step, lower);
-        HIP_TRY(cude::launch_fill(N, x, f.c, c->stream));
-        if (k == 1 && (rc = maybe_regroup(c))) return rc;     // (adaptive mode: the first probe has told the step counts)
-        if ((rc = run_ensemble(c, false, nullptr, true, f.c, sse_c))) return rc;
-        HIP_TRY(cude::launch_fit(0, f, k, x, c->stream));
-    }
-    HIP_TRY(cude::launch_fit(1, f, 0, 0.0, c->stream));
-    for (int it = 0; it < n_iters; it++) {                // golden section inside the bracket
-        if ((rc = run_ensemble(c, false, nullptr, true, f.c, sse_c))) return rc;
-        if ((rc = run_ensemble(c, false, nullptr, true, f.d, sse_d))) return rc;
-        HIP_TRY(cude::launch_fit(2, f, it == n_iters - 1 ? 1 : 0, 0.0, c->stream));
+    } else {
+        // one probe per launch; everything is queued on the stream, the only synchronisation is the copy-back at the end
+        for (int k = 0; k < n_grid; k++) {                    // coarse scan of the box
+            const double x = (k == n_grid - 1) ? upper : std::fma((double)k, f.step, lower);
+            HIP_TRY(cude::launch_fill(N, x, f.c, c->stream));
+            if (k == 1 && (rc = maybe_regroup(c))) return rc;     // (adaptive mode: the first probe has told the step counts)
+            if ((rc = run_ensemble(c, false, nullptr, true, f.c, sse_c))) return rc;
+            HIP_TRY(cude::launch_fit(0, f, k, x, c->stream));
+        }
+        HIP_TRY(cude::launch_fit(1, f, 0, 0.0, c->stream));
+        for (int it = 0; it < n_iters; it++) {                // golden section inside the bracket
+            if ((rc = run_ensemble(c, false, nullptr, true, f.c, sse_c))) return rc;
+            if ((rc = run_ensemble(c, false, nullptr, true, f.d, sse_d))) return rc;
+            HIP_TRY(cude::launch_fit(2, f, it == n_iters - 1 ? 1 : 0, 0.0, c->stream));
+        }
     }
     if ((rc = run_ensemble(c, false, nullptr, true, f.c, sse_c))) return rc;       // at the returned midpoint
     HIP_TRY(cude::launch_fit(3, f, 0, 0.0, c->stream));
@@ -1450,7 +1468,7 @@ namespace {
 int mh_spec_depth(const cude_ctx* c, int n_mc) {
     int d = c->opt.mh_spec;
     if (d < 0) {
-        const int64_t waves1 = c->nblocks * (c->chunks_f > 1 ? c->chunks_f : c->chunks);
+        const int64_t waves1 = c->nblocks * forward_chunks(c);
         d = 7 * waves1 <= 2048 ? 3 : (3 * waves1 <= 2400 ? 2 : 0);
     }
     d = std::min(d, cude::kMhSpecMaxDepth);
@@ -1471,6 +1489,76 @@ int mh_spec_depth_one_launch(const cude_ctx* c, int n_mc) {
     d = std::min(d, cude::kMhSpecMaxDepth);
     if (d > n_mc) d = n_mc;
     return d >= 2 ? d : 0;
+}
+
+// gamma < 1, the proposal and both possible next states in one launch: d such steps per launch by speculation
+// (MhSpecArgs::blend: a node of the candidate heap is its state AND its proposal, 2 (2^d - 1) parameter sets) while the
+// sets' waves still have a SIMD each
+// (profiles/r05/estep_speculative.txt, gamma = 0.25, 100 steps, ms per E-step two launches per step -> one -> depth
+//  2 / 3: adaptive 57 subjects 20.3 -> 11.0 -> 5.6 / 4.0, 4 000: 24.0 -> 12.8 -> 8.7 / 6.0, 1e4: 24.3 -> 17.3 -> 8.7 /
+//  11.5; fixed 30 steps (time-split) 57: 4.10 -> 2.39 -> 1.27 / 1.01, 1 000: 4.06 -> 2.39 -> 1.51 / 1.57, 4 000:
+//  4.28 -> 3.68 -> 3.02 / 3.61, 1e4: 5.94 -> 6.17 -> 5.10 / 6.62)
+int mh_spec_depth_blend(const cude_ctx* c, int n_mc, bool split) {
+    int d = c->opt.mh_spec;
+    if (d < 0) {
+        const int64_t waves1 = c->nblocks * (split ? forward_chunks(c) : 1);
+        if (split) d = 14 * waves1 <= 2048 ? 3 : (6 * waves1 <= 6000 ? 2 : 0);
+        else d = 14 * waves1 <= 1024 ? 3 : (6 * waves1 <= 1024 ? 2 : 0);
+    }
+    d = std::min(std::min(d, (int)cude::kMhSpecMaxDepthBlend), n_mc);
+    return d >= 2 ? d : 0;
+}
+
+// How cude_mh_chain speculates (MhSpecArgs, cude_kernels.h): `depth` steps per dependent launch chain -- the candidate
+// states those steps can reach as parameter sets of ONE forward launch, then the resolver of the decisions behind their SSEs.
+struct SpecRounds {
+    int depth = 0;                      // < 2: no speculation
+    bool blend = false;                 // gamma < 1 (MhSpecArgs::blend)
+    bool split = false;                 // the candidates' forward launch is time-split
+    bool resolve_in_scan = false;       // ... and its scan launch, which then holds a subject's candidates in one workgroup,
+                                        // resolves the round; otherwise a launch_mh_spec of its own does
+    int sets(int d) const { return (blend ? 2 : 1) * ((1 << d) - 1); }
+};
+
+// The n_mc steps of the chain in rounds of p.depth.  z / u: the caller's draws on the device (null: the context's
+// generator); states: where the chain state after every step goes, or null; cand: sets(depth) rows of N; fwd: the forward
+// launch of the candidates (at `cand`, SSEs to fwd.sse), its n_sets filled in here round by round.
+int32_t mh_spec_rounds(cude_ctx* c, const SpecRounds& p, const cude::MhArgs& m, double proposal_std, int n_mc,
+                       const double* z, const double* u, double* states, double* cand, SetsForward fwd) {
+    int32_t rc = CUDE_OK;
+    const int64_t N = c->N;
+    cude::MhSpecArgs sa{};
+    sa.mh = m;
+    sa.mh.key = cude::RngKey{c->rng_seed, c->rng_offset, 0};
+    sa.blend = p.blend ? 1 : 0;
+    sa.cand = cand; sa.sse_sets = fwd.sse; sa.proposal_std = proposal_std;
+    sa.depth_resolve = 0; sa.depth_next = std::min(p.depth, n_mc);
+    sa.step_resolve = sa.step_next = c->rng_step;
+    sa.z_rows = z;
+    HIP_TRY(cude::launch_mh_spec(sa, c->stream));                 // the first round's candidates
+    int round = 0;
+    for (int k = 0; k < n_mc; round++) {
+        const int d = std::min(p.depth, n_mc - k);
+        sa.depth_resolve = d;
+        sa.depth_next = std::min(p.depth, n_mc - k - d);
+        sa.step_resolve = c->rng_step + k;
+        sa.step_next = c->rng_step + k + d;
+        sa.u_rows = u ? u + (size_t)k * N : nullptr;
+        sa.z_rows = z ? z + (size_t)(k + d) * N : nullptr;
+        // (caller's draws + samples: the states of steps k .. k+d-1 overwrite the normals of those steps, which the
+        //  PREVIOUS resolver consumed; the next round's normals are rows k+d ...)
+        sa.samples = states ? states + (size_t)k * N : nullptr;
+        fwd.n_sets = p.sets(d);
+        fwd.resolve_in_scan = p.resolve_in_scan ? &sa : nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        // kernel timing: every 4th round, and only where the forward launch is the whole round
+        if (p.resolve_in_scan && c->timing && round % 4 == 0 && (rc = timed_pair(c, &e0, &e1))) return rc;
+        if ((rc = forward_sets(c, fwd))) return rc;
+        if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
+        if (!p.resolve_in_scan) HIP_TRY(cude::launch_mh_spec(sa, c->stream));
+        k += d;
+    }
+    return CUDE_OK;
 }
 }  // namespace
 
@@ -1519,270 +1607,85 @@ int32_t cude_mh_chain(cude_ctx* c, int32_t n_mc, const double* normals, const do
     // Time-split forward path + carried SSE: the proposal is formed inside the forward chunks and accepted inside the
     // scan (Cpep2Args::mh_fused) -- two launches per Metropolis step instead of four, same bits.
     const bool fused = m.carry_sse && is_cpep(c) && !adaptive(c) && c->chunks > 1 && c->opt.mh_fuse;
-    // Speculative steps (MhSpecArgs, cude_kernels.h): d steps per dependent launch pair -- forward chunks of the 2^d - 1
-    // candidate states as parameter sets of ONE launch, then a scan launch that holds a subject's candidates in one
-    // workgroup and resolves the d decisions behind their SSEs -- instead of one pair per step.
-    // Pays while the candidates still fit the chip beside each other (a shard of an E-step spread over 8 GPUs).
-    const int spec = fused ? mh_spec_depth(c, n_mc) : 0;
-    if (spec >= 2) {
-        const int P = c->P, Lf = (c->chunks_f > 1 ? c->chunks_f : c->chunks), T = c->T;
-        const int64_t nb = c->nblocks, max_sets = (1 << spec) - 1;
-        DevBuf<double> d_cand, d_sse_sets;
-        HIP_TRY(d_cand.resize((size_t)max_sets * N));
-        HIP_TRY(d_sse_sets.resize((size_t)max_sets * N));
-        HIP_TRY(c->ms_fsum.reserve((size_t)max_sets * Lf * (3 + T) * N));
-        HIP_TRY(c->ms_part.reserve((size_t)max_sets * nb * (P + 2)));
-        cude::MhSpecArgs sa{};
-        sa.mh = m;
-        sa.mh.key = cude::RngKey{c->rng_seed, c->rng_offset, 0};
-        sa.cand = d_cand.p; sa.sse_sets = d_sse_sets.p; sa.proposal_std = proposal_std;
-        sa.depth_resolve = 0; sa.depth_next = std::min(spec, n_mc);
-        sa.step_resolve = sa.step_next = c->rng_step;
-        sa.z_rows = device_rng ? nullptr : d_z.p;
-        HIP_TRY(cude::launch_mh_spec(sa, c->stream));                 // the first round's candidates
-        int round = 0;
-        for (int k = 0; k < n_mc; round++) {
-            const int d = std::min(spec, n_mc - k), sets = (1 << d) - 1;
-            cude::CpepArgs a = cpep_args(c);
-            a.cond = d_cand.p; a.nn = c->nn.p; a.sse = d_sse_sets.p; a.traj = nullptr; a.auc = nullptr;
-            a.g_cond = c->g_cond.p; a.partials = c->ms_part.p;
-            a.n_sets = sets; a.set_stride_nn = 0; a.set_stride_cond = N;       // one network, `sets` candidate states
-            cude::Cpep2Args a2 = chunk_args(c, a, /*all_blocks=*/true, /*forward_only=*/true);
-            a2.fsum = c->ms_fsum.p;
-            sa.depth_resolve = d;
-            sa.depth_next = std::min(spec, n_mc - k - d);
-            sa.step_resolve = c->rng_step + k;
-            sa.step_next = c->rng_step + k + d;
-            sa.u_rows = device_rng ? nullptr : d_u.p + (size_t)k * N;
-            sa.z_rows = device_rng ? nullptr : d_z.p + (size_t)(k + d) * N;
-            // (caller's draws + samples: the states of steps k .. k+d-1 overwrite the normals of those steps, which the
-            //  PREVIOUS resolver consumed; the next round's normals are rows k+d ...)
-            sa.samples = samples ? d_z.p + (size_t)k * N : nullptr;
-            a2.spec_slots = 1 << d;             // the scan launch resolves the round itself
-            a2.spec = sa;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (c->timing && round % 4 == 0) {
-                if (c->ev_used == c->ev_pool.size()) {
-                    hipEvent_t ea, eb;
-                    HIP_TRY(hipEventCreate(&ea));
-                    HIP_TRY(hipEventCreate(&eb));
-                    c->ev_pool.emplace_back(ea, eb);
-                }
-                e0 = c->ev_pool[c->ev_used].first; e1 = c->ev_pool[c->ev_used].second;
-                c->ev_used++;
-                HIP_TRY(hipEventRecord(e0, c->stream));
-            }
-            HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, false, a2, c->stream));
-            if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
-            k += d;
-        }
-        if (samples)
-            HIP_TRY(hipMemcpyAsync(samples, d_z.p, (size_t)n_mc * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (accepted) HIP_TRY(hipMemcpyAsync(accepted, d_acc.p, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (device_rng) c->rng_step += n_mc;
-        return CUDE_OK;
-    }
-    const int spec1 = (!fused && m.carry_sse && is_cpep(c) && (adaptive(c) || c->chunks <= 1) && !c->net.generic())
-                          ? mh_spec_depth_one_launch(c, n_mc) : 0;
-    if (spec1 >= 2) {
-        const int P = c->P;
-        const int64_t nb = c->nblocks, max_sets = (1 << spec1) - 1;
-        DevBuf<double> d_cand, d_sse_sets, d_part;
-        HIP_TRY(d_cand.resize((size_t)max_sets * N));
-        HIP_TRY(d_sse_sets.resize((size_t)max_sets * N));
-        HIP_TRY(d_part.resize((size_t)max_sets * nb * (P + 2)));
-        cude::MhSpecArgs sa{};
-        sa.mh = m;
-        sa.mh.key = cude::RngKey{c->rng_seed, c->rng_offset, 0};
-        sa.cand = d_cand.p; sa.sse_sets = d_sse_sets.p; sa.proposal_std = proposal_std;
-        sa.depth_resolve = 0; sa.depth_next = std::min(spec1, n_mc);
-        sa.step_resolve = sa.step_next = c->rng_step;
-        sa.z_rows = device_rng ? nullptr : d_z.p;
-        HIP_TRY(cude::launch_mh_spec(sa, c->stream));                 // the first round's candidates
-        for (int k = 0; k < n_mc;) {
-            const int d = std::min(spec1, n_mc - k), sets = (1 << d) - 1;
-            cude::CpepArgs a = cpep_args(c);
-            a.cond = d_cand.p; a.nn = c->nn.p; a.sse = d_sse_sets.p; a.traj = nullptr; a.auc = nullptr;
-            a.g_cond = c->g_cond.p; a.partials = d_part.p;
-            a.n_sets = sets; a.set_stride_nn = 0; a.set_stride_cond = N;       // one network, `sets` candidate states
-            HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
-            sa.depth_resolve = d;
-            sa.depth_next = std::min(spec1, n_mc - k - d);
-            sa.step_resolve = c->rng_step + k;
-            sa.step_next = c->rng_step + k + d;
-            sa.u_rows = device_rng ? nullptr : d_u.p + (size_t)k * N;
-            sa.z_rows = device_rng ? nullptr : d_z.p + (size_t)(k + d) * N;
-            sa.samples = samples ? d_z.p + (size_t)k * N : nullptr;            // (as in the time-split rounds above)
-            HIP_TRY(cude::launch_mh_spec(sa, c->stream));
-            k += d;
-        }
-        if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }      // (step counts of the last round's set 0)
-        if (samples)
-            HIP_TRY(hipMemcpyAsync(samples, d_z.p, (size_t)n_mc * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (accepted) HIP_TRY(hipMemcpyAsync(accepted, d_acc.p, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (device_rng) c->rng_step += n_mc;
-        return CUDE_OK;
-    }
     // gamma < 1 (the stochastic-approximation phase): the next state is a blend whose likelihood is not known, so a step
     // needed two solves one after the other (the proposal, then the current state again).  The two possible next states
     // depend on (p, q, gamma) alone: they are solved in the SAME launch as the proposal, as three parameter sets, and the
     // decision picks state and SSE (mh_accept_blend_kernel) -- one solve launch per step, the same chain.
-    if (!m.carry_sse && is_cpep(c) && !c->net.generic() && c->opt.mh_pair) {
-        const int P = c->P, sets = 3;
-        const int64_t nb = c->nblocks;
-        const bool split = !adaptive(c) && c->chunks > 1;
-        DevBuf<double> d_cand, d_sse3, d_part;
-        HIP_TRY(d_cand.resize((size_t)sets * N));
-        HIP_TRY(d_sse3.resize((size_t)sets * N));
-        if (split) {
-            const int Lf = (c->chunks_f > 1 ? c->chunks_f : c->chunks);
-            HIP_TRY(c->ms_fsum.reserve((size_t)sets * Lf * (3 + c->T) * N));
-            HIP_TRY(c->ms_part.reserve((size_t)sets * nb * (P + 2)));
-        } else {
-            HIP_TRY(d_part.resize((size_t)sets * nb * (P + 2)));
-        }
-        // ... and d such steps per launch by speculation (MhSpecArgs::blend: a node of the candidate heap is its state AND
-        // its proposal, 2 (2^d - 1) parameter sets) while the sets' waves still have a SIMD each
-        int spec3 = c->opt.mh_spec;
-        {
-            const int64_t waves1 = nb * (split ? (c->chunks_f > 1 ? c->chunks_f : c->chunks) : 1);
-            // (profiles/r05/estep_speculative.txt, gamma = 0.25, 100 steps, ms per E-step two launches per step -> one -> depth
-            //  2 / 3: adaptive 57 subjects 20.3 -> 11.0 -> 5.6 / 4.0, 4 000: 24.0 -> 12.8 -> 8.7 / 6.0, 1e4: 24.3 -> 17.3 -> 8.7 /
-            //  11.5; fixed 30 steps (time-split) 57: 4.10 -> 2.39 -> 1.27 / 1.01, 1 000: 4.06 -> 2.39 -> 1.51 / 1.57, 4 000:
-            //  4.28 -> 3.68 -> 3.02 / 3.61, 1e4: 5.94 -> 6.17 -> 5.10 / 6.62)
-            if (spec3 < 0) {
-                if (split) spec3 = 14 * waves1 <= 2048 ? 3 : (6 * waves1 <= 6000 ? 2 : 0);
-                else spec3 = 14 * waves1 <= 1024 ? 3 : (6 * waves1 <= 1024 ? 2 : 0);
-            }
-            spec3 = std::min(std::min(spec3, (int)cude::kMhSpecMaxDepthBlend), (int)n_mc);
-            if (spec3 < 2) spec3 = 0;
-        }
-        if (spec3 >= 2) {
-            const int64_t max_sets = 2 * ((1 << spec3) - 1);
-            HIP_TRY(d_cand.resize((size_t)max_sets * N));
-            HIP_TRY(d_sse3.resize((size_t)max_sets * N));
-            if (split) {
-                const int Lf = (c->chunks_f > 1 ? c->chunks_f : c->chunks);
-                HIP_TRY(c->ms_fsum.reserve((size_t)max_sets * Lf * (3 + c->T) * N));
-                HIP_TRY(c->ms_part.reserve((size_t)max_sets * nb * (P + 2)));
-            } else {
-                HIP_TRY(d_part.resize((size_t)max_sets * nb * (P + 2)));
-            }
-            cude::MhSpecArgs sa{};
-            sa.mh = m;
-            sa.mh.key = cude::RngKey{c->rng_seed, c->rng_offset, 0};
-            sa.blend = 1;
-            sa.cand = d_cand.p; sa.sse_sets = d_sse3.p; sa.proposal_std = proposal_std;
-            sa.depth_resolve = 0; sa.depth_next = std::min(spec3, n_mc);
-            sa.step_resolve = sa.step_next = c->rng_step;
-            sa.z_rows = device_rng ? nullptr : d_z.p;
-            HIP_TRY(cude::launch_mh_spec(sa, c->stream));             // the first round's candidates
-            for (int k = 0; k < n_mc;) {
-                const int d = std::min(spec3, n_mc - k), nsets = 2 * ((1 << d) - 1);
-                cude::CpepArgs a = cpep_args(c);
-                a.cond = d_cand.p; a.nn = c->nn.p; a.sse = d_sse3.p; a.traj = nullptr; a.auc = nullptr;
-                a.g_cond = c->g_cond.p; a.partials = split ? c->ms_part.p : d_part.p;
-                a.n_sets = nsets; a.set_stride_nn = 0; a.set_stride_cond = N;
-                if (split) {
-                    cude::Cpep2Args a2 = chunk_args(c, a, /*all_blocks=*/true, /*forward_only=*/true);
-                    a2.fsum = c->ms_fsum.p;
-                    HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, false, a2, c->stream));
-                } else {
-                    HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
-                }
-                sa.depth_resolve = d;
-                sa.depth_next = std::min(spec3, n_mc - k - d);
-                sa.step_resolve = c->rng_step + k;
-                sa.step_next = c->rng_step + k + d;
-                sa.u_rows = device_rng ? nullptr : d_u.p + (size_t)k * N;
-                sa.z_rows = device_rng ? nullptr : d_z.p + (size_t)(k + d) * N;
-                sa.samples = samples ? d_z.p + (size_t)k * N : nullptr;
-                HIP_TRY(cude::launch_mh_spec(sa, c->stream));
-                k += d;
-            }
-            if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
-            if (samples)
-                HIP_TRY(hipMemcpyAsync(samples, d_z.p, (size_t)n_mc * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            if (accepted) HIP_TRY(hipMemcpyAsync(accepted, d_acc.p, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (device_rng) c->rng_step += n_mc;
-            return CUDE_OK;
-        }
+    const bool pair = !m.carry_sse && is_cpep(c) && !c->net.generic() && c->opt.mh_pair;
+    // Speculative steps (MhSpecArgs, cude_kernels.h): d steps per dependent launch pair -- forward chunks of the 2^d - 1
+    // candidate states as parameter sets of ONE launch, then a scan launch that holds a subject's candidates in one
+    // workgroup and resolves the d decisions behind their SSEs -- instead of one pair per step.
+    // Pays while the candidates still fit the chip beside each other (a shard of an E-step spread over 8 GPUs).
+    SpecRounds sp;
+    if (fused) {
+        sp.depth = mh_spec_depth(c, n_mc);
+        sp.split = sp.resolve_in_scan = true;
+    } else if (m.carry_sse && is_cpep(c) && (adaptive(c) || c->chunks <= 1) && !c->net.generic()) {
+        sp.depth = mh_spec_depth_one_launch(c, n_mc);
+    } else if (pair) {
+        sp.blend = true;
+        sp.split = !adaptive(c) && c->chunks > 1;
+        sp.depth = mh_spec_depth_blend(c, n_mc, sp.split);
+    }
+    // parameter sets per forward launch: a round's candidates, the three of a blend step, or none (one solve per launch)
+    const int max_sets = sp.depth >= 2 ? sp.sets(sp.depth) : (pair ? 3 : 0);
+    DevBuf<double> d_cand, d_sse_sets, d_part;
+    SetsForward fwd;                                      // one network, the candidate states
+    if (max_sets > 0) {
+        HIP_TRY(d_cand.resize((size_t)max_sets * N));
+        HIP_TRY(d_sse_sets.resize((size_t)max_sets * N));
+        if ((rc = reserve_sets_forward(c, max_sets, sp.split, d_part))) return rc;
+        fwd.cond = d_cand.p; fwd.nn = c->nn.p; fwd.sse = d_sse_sets.p; fwd.partials = d_part.p; fwd.split = sp.split;
+    }
+    const double* const z = device_rng ? nullptr : d_z.p;
+    const double* const u = d_u.p;                        // (null with device draws)
+    if (sp.depth >= 2) {
+        if ((rc = mh_spec_rounds(c, sp, m, proposal_std, n_mc, z, u, samples ? d_z.p : nullptr, d_cand.p, fwd))) return rc;
+    } else if (pair) {
         if ((rc = run_ensemble(c, false, nullptr, true, c->cond.p, d_sc.p))) return rc;      // SSE of the starting state
+        fwd.n_sets = 3;
         for (int k = 0; k < n_mc; k++) {
             m.key = cude::RngKey{c->rng_seed, c->rng_offset, c->rng_step + k};
-            HIP_TRY(cude::launch_mh_blend_candidates(N, c->cond.p, device_rng ? nullptr : d_z.p + (size_t)k * N, m.key,
-                                                     proposal_std, gamma, d_cand.p, c->stream));
-            cude::CpepArgs a = cpep_args(c);
-            a.cond = d_cand.p; a.nn = c->nn.p; a.sse = d_sse3.p; a.traj = nullptr; a.auc = nullptr;
-            a.g_cond = c->g_cond.p; a.partials = split ? c->ms_part.p : d_part.p;
-            a.n_sets = sets; a.set_stride_nn = 0; a.set_stride_cond = N;       // one network, three candidate states
-            if (split) {
+            HIP_TRY(cude::launch_mh_blend_candidates(N, c->cond.p, z ? z + (size_t)k * N : nullptr, m.key, proposal_std, gamma,
+                                                     d_cand.p, c->stream));
+            if ((rc = forward_sets(c, fwd))) return rc;
+            m.u = u ? u + (size_t)k * N : nullptr;
+            HIP_TRY(cude::launch_mh_accept_blend(m, d_cand.p, d_sse_sets.p, c->stream));
+            if (samples)
+                HIP_TRY(hipMemcpyAsync(d_z.p + (size_t)k * N, c->cond.p, N * sizeof(double), hipMemcpyDeviceToDevice,
+                                       c->stream));
+        }
+    } else {
+        for (int k = 0; k < n_mc; k++) {          // everything is queued on the stream; one sync at the end
+            m.key = cude::RngKey{c->rng_seed, c->rng_offset, c->rng_step + k};
+            m.u = u ? u + (size_t)k * N : nullptr;
+            if (fused) {
+                m.prop = nullptr; m.sse_new = nullptr;
+                cude::CpepArgs a = cpep_args(c);
+                a.cond = c->cond.p; a.nn = c->nn.p; a.sse = d_sn.p; a.traj = nullptr; a.auc = c->auc.p;
+                a.g_cond = c->g_cond.p; a.partials = c->partials.p;
                 cude::Cpep2Args a2 = chunk_args(c, a, /*all_blocks=*/true, /*forward_only=*/true);
-                a2.fsum = c->ms_fsum.p;
+                a2.mh_fused = 1;
+                a2.mh_z = z ? z + (size_t)k * N : nullptr;
+                a2.mh_std = proposal_std;
+                a2.mh = m;
+                hipEvent_t e0 = nullptr, e1 = nullptr;
+                // kernel timing: a pair of events costs ~4.5 us of stream time, 10 % of a Metropolis step at 1e4 subjects, so
+                // inside this loop of identical launches every 8th step is timed (cude_kernel_time_ms averages those)
+                if (c->timing && k % 8 == 0 && (rc = timed_pair(c, &e0, &e1))) return rc;
                 HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, false, a2, c->stream));
+                if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
             } else {
-                HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, false, a, c->stream));
+                HIP_TRY(cude::launch_mh_propose(N, c->cond.p, z ? z + (size_t)k * N : nullptr, m.key, proposal_std, d_prop.p,
+                                                c->stream));
+                if ((rc = run_ensemble(c, false, nullptr, true, d_prop.p, d_sn.p))) return rc;
+                if (!m.carry_sse && (rc = run_ensemble(c, false, nullptr, true, c->cond.p, d_sc.p))) return rc;
+                HIP_TRY(cude::launch_mh_accept(m, c->stream));
             }
-            m.u = device_rng ? nullptr : d_u.p + (size_t)k * N;
-            HIP_TRY(cude::launch_mh_accept_blend(m, d_cand.p, d_sse3.p, c->stream));
-            if (samples)
+            if (samples)       // chain state after step k (the draws of this step are no longer needed: reuse their row)
                 HIP_TRY(hipMemcpyAsync(d_z.p + (size_t)k * N, c->cond.p, N * sizeof(double), hipMemcpyDeviceToDevice,
                                        c->stream));
         }
-        if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
-        if (samples)
-            HIP_TRY(hipMemcpyAsync(samples, d_z.p, (size_t)n_mc * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (accepted) HIP_TRY(hipMemcpyAsync(accepted, d_acc.p, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (device_rng) c->rng_step += n_mc;
-        return CUDE_OK;
-    }
-    for (int k = 0; k < n_mc; k++) {          // everything is queued on the stream; one sync at the end
-        m.key = cude::RngKey{c->rng_seed, c->rng_offset, c->rng_step + k};
-        if (fused) {
-            m.u = device_rng ? nullptr : d_u.p + (size_t)k * N;
-            m.prop = nullptr; m.sse_new = nullptr;
-            cude::CpepArgs a = cpep_args(c);
-            a.cond = c->cond.p; a.nn = c->nn.p; a.sse = d_sn.p; a.traj = nullptr; a.auc = c->auc.p;
-            a.g_cond = c->g_cond.p; a.partials = c->partials.p;
-            cude::Cpep2Args a2 = chunk_args(c, a, /*all_blocks=*/true, /*forward_only=*/true);
-            a2.mh_fused = 1;
-            a2.mh_z = device_rng ? nullptr : d_z.p + (size_t)k * N;
-            a2.mh_std = proposal_std;
-            a2.mh = m;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            // kernel timing: a pair of events costs ~4.5 us of stream time, 10 % of a Metropolis step at 1e4 subjects, so
-            // inside this loop of identical launches every 8th step is timed (cude_kernel_time_ms averages those)
-            if (c->timing && k % 8 == 0) {
-                if (c->ev_used == c->ev_pool.size()) {
-                    hipEvent_t ea, eb;
-                    HIP_TRY(hipEventCreate(&ea));
-                    HIP_TRY(hipEventCreate(&eb));
-                    c->ev_pool.emplace_back(ea, eb);
-                }
-                e0 = c->ev_pool[c->ev_used].first; e1 = c->ev_pool[c->ev_used].second;
-                c->ev_used++;
-                HIP_TRY(hipEventRecord(e0, c->stream));
-            }
-            HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, false, a2, c->stream));
-            if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
-            if (samples)
-                HIP_TRY(hipMemcpyAsync(d_z.p + (size_t)k * N, c->cond.p, N * sizeof(double), hipMemcpyDeviceToDevice,
-                                       c->stream));
-            continue;
-        }
-        HIP_TRY(cude::launch_mh_propose(N, c->cond.p, device_rng ? nullptr : d_z.p + (size_t)k * N, m.key, proposal_std,
-                                        d_prop.p, c->stream));
-        if ((rc = run_ensemble(c, false, nullptr, true, d_prop.p, d_sn.p))) return rc;
-        if (!m.carry_sse && (rc = run_ensemble(c, false, nullptr, true, c->cond.p, d_sc.p))) return rc;
-        m.u = device_rng ? nullptr : d_u.p + (size_t)k * N;
-        HIP_TRY(cude::launch_mh_accept(m, c->stream));
-        if (samples)       // chain state after step k (the draws of this step are no longer needed: reuse their row)
-            HIP_TRY(hipMemcpyAsync(d_z.p + (size_t)k * N, c->cond.p, N * sizeof(double), hipMemcpyDeviceToDevice,
-                                   c->stream));
     }
     if (samples)
         HIP_TRY(hipMemcpyAsync(samples, d_z.p, (size_t)n_mc * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
