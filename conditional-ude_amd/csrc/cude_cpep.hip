@@ -29,7 +29,7 @@ namespace cude {
 // becomes HBM-bound at ~3.7 TB/s of mixed streaming -- 125 000 subjects 0.564 -> 0.578 ms, 1e6 4.18 -> 4.64 ms, 1e5 (mixed
 // launch) 0.492 -> 0.476 ms, 65 536 unchanged (profiles/r03/keep_activations.txt).  Not enabled: CUDE_CPEP_KEEP=1 selects it.
 template <class Net, int NS, bool GRAD, int KEEP = 0>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KEEP != 0 ? 2 : 1))) void cpep_kernel(CpepArgs a) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP != 0 || (GRAD && Net::HAS_RW)) ? 2 : 1))) void cpep_kernel(CpepArgs a) {
     constexpr int P = Net::P;
     constexpr int NC = Net::NC;
     constexpr int TABROWS = Net::HAS_TAB ? 5 * Net::NCST : 0;
@@ -260,6 +260,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KEEP != 
         double acc[Net::NACC];
 #pragma unroll
         for (int q = 0; q < Net::NACC; q++) acc[q] = 0.0;
+        // the hidden layer of this launch row's parameter set, held in SGPRs for all 5 S + 1 reverse evaluations
+#ifndef CUDE_NO_RW
+        constexpr bool kRW = Net::HAS_RW && KEEP == 0;
+#else
+        constexpr bool kRW = false;
+#endif
+        typename Net::RW rw;
+        if constexpr (kRW) Net::load_rw(a.nn + set * a.set_stride_nn, lane, rw);
         double dxdummy[1] = {0.0};
         double lam1 = 0.0, lam2 = 0.0;       // adjoint of y_{n+1}
         double kap1 = 0.0, kap2 = 0.0;       // adjoint of k_1 of step n+1 (= k_7 of step n)
@@ -362,6 +370,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KEEP != 
             }
             double xv = 0.0, wv;
             bool tab = false;
+            typename Net::RS rs;
+            if constexpr (kRW) Net::rw_request(p, rs);   // travels with seg[e] and phi[e]: one scalar round trip
             if (e >= 0) {
                 const int sg = seg[e];
                 const double ph = phi[e];
@@ -412,13 +422,28 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KEEP != 
                 }
                 Net::layer1(p, c, x, hk[0], tab, &E1);
                 Net::template backward<false>(launder(p), x, hk, sg, wv, acc, dxdummy);
+            } else if constexpr (kRW) {
+                Net::eval_grad_rw(p, rw, rs, c, x, wv, acc, tab, &E1);
             } else {
                 Net::template eval_grad<false>(p, c, x, wv, acc, dxdummy, tab, &E1);
             }
         }
 
+        if constexpr (kRW) {
+            // the subject index and exp(beta) are formed again here: carried through the sweep, their four registers
+            // are the ones the resident layer needs
+            int le = lane;
+            asm volatile("" : "+v"(le));
+            const int64_t ge = (int64_t)blockIdx.x * kBlock + le;
+            const int64_t ie = ge < a.N ? ge : a.N - 1;
+            double ce[NC];
+            ce[0] = Net::cond_input(a.cond[set * a.set_stride_cond + ie]);
+            if (active) a.g_cond[set * a.set_stride_cond + ie] = Net::grad_cond(p, acc, ce);
+            block_reduce_expand<Net, NC>(acc, ce, active ? 1.0 : 0.0, red_loss, red_fail, s_red, out, lane);
+        } else {
         if (active) a.g_cond[set * a.set_stride_cond + i] = Net::grad_cond(p, acc, cst);
         block_reduce_expand<Net, NC>(acc, cst, active ? 1.0 : 0.0, red_loss, red_fail, s_red, out, lane);
+        }
 #ifdef CUDE_WAVE_TIMING
         if (a.dbg != nullptr && lane == 0 && blockIdx.y == 0) {
             long long* d = a.dbg + 4 * (long long)blockIdx.x;

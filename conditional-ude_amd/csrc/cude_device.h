@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "cude_kernels.h"
 #include "cude_math.h"
 
@@ -755,6 +757,155 @@ struct Mlp {
         return y;
     }
 
+    // ---- value + weighted reverse sweep with the hidden layer RESIDENT ACROSS THE SWEEP, LANE-PACKED IN VGPRS (reverse
+    // sweep of the fixed-step c-peptide gradient kernel, which reads the same W x W + W doubles in every one of its
+    // 5 S + 1 evaluations).  Neither register file has room for a plain copy: 72 SGPRs next to the loop's own ~60 spill
+    // to VGPR lanes (113 v_readlane / v_writelane per evaluation), 72 VGPRs next to the 122 of the accumulators cost the
+    // second wave.  But the weights are wave-uniform, so one VGPR pair can hold SIXTEEN of them, one per lane of a row
+    // of 16 lanes, the same in all four rows, and v_fmac_f64 takes such an operand through DPP row_newbcast: the lane's
+    // value is broadcast within its row while the instruction reads it.  W x W + W = 42 doubles in three VGPR pairs, no
+    // scalar load, no wait and no SGPR for the layer inside the loop; the constants of the exponentials, which the full
+    // SGPR file made the compiler rebuild in every evaluation (38 s_mov_b32), stay put as well.
+    //  * Only the multiply-add has the DPP form on gfx950 (v_mul_f64 is VOP3-only), so the transposed product's two
+    //    partial sums start from an explicit zero: 12 v_mov_b64 per evaluation that the scalar form did not need (the
+    //    14 v_readlane it needed are gone).  fma(w, d, 0) and 0 + w * d are the same operation: results are unchanged
+    //    bit for bit.
+    //  * What still streams -- the output unit's weights and bias, 14 dwords -- is requested by the caller at the top of
+    //    the evaluation (rw_request), together with its own scalar reads.
+    //  * DPP hazards (a VALU write of the DPP source needs two instructions' distance, a VALU write of EXEC five) are
+    //    the compiler's business only for instructions it selects itself: the packed registers are written once, in
+    //    front of the loop (load_rw), and the evaluation runs in wave-uniform control flow.
+    static constexpr bool HAS_RW = HAS_VW && HAS_PF && HAS_TAB && !TT && D == 2 && NIN == 2 && NV == 1 && W == 6;
+    static constexpr int NRW = (W * W + W + 15) / 16;     // slots: the W x W weights in parameter order, then the W biases
+    struct RW {
+        double w[HAS_RW ? NRW : 1];
+    };
+    struct RS {                                           // the scalar operands of one evaluation
+        SCol<W> wo;
+        double bo;
+    };
+    __device__ static __forceinline__ void load_rw(const double* p, int lane, RW& r) {
+#pragma unroll
+        for (int k = 0; k < NRW; k++) {
+            const int q = 16 * k + (lane & 15);
+            double t = p[L1 + (q < W * W + W ? q : W * W + W - 1)];
+            asm volatile("" : "+v"(t));              // pin the copy (no re-materialising load inside the loop)
+            r.w[k] = t;
+        }
+    }
+    __device__ static __forceinline__ void rw_request(cptr_t p, RS& rs) {
+        rs.wo = ld_col<W>(p, OUT);
+        rs.bo = launder(p)[OUT + W];
+    }
+    // fma(slot Q, b, acc) and slot Q itself
+    template <int Q>
+    __device__ static __forceinline__ double rw_fma(const RW& r, double b, double acc) {
+        asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(acc)
+            : "v"(r.w[Q / 16]), "v"(b), "n"(Q % 16));
+        return acc;
+    }
+    template <int Q>
+    __device__ static __forceinline__ double rw_get(const RW& r) {
+        double v;
+        asm("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(v) : "v"(r.w[Q / 16]), "n"(Q % 16));
+        return v;
+    }
+    // f(I, J) for I, J in [0, N) as compile-time constants (the slot of rw_fma is an immediate of the instruction)
+    template <int I, int J, int N, class F>
+    __device__ static __forceinline__ void rw_for(F&& f) {
+        if constexpr (I < N) {
+            f(std::integral_constant<int, I>{}, std::integral_constant<int, J>{});
+            if constexpr (J + 1 < N) rw_for<I, J + 1, N>(f);
+            else rw_for<I + 1, 0, N>(f);
+        }
+    }
+    // m_tanh_vec for pre-activations that come out of rw_fma.  The compiler cannot see that an inline-asm result is
+    // no signalling NaN and would put a canonicalising v_max in front of every clamp; the clamp min(|z|, 20) is
+    // therefore written as the instruction it compiles to elsewhere.
+    __device__ static __forceinline__ void rw_tanh(const double (&z)[W], double (&t)[W]) {
+        double d[W], pre[W];
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            double a;
+            asm("v_min_f64 %0, |%1|, %2" : "=v"(a) : "v"(z[j]), "s"(20.0));
+            d[j] = m_exp2x(a) + 1.0;
+        }
+        pre[0] = d[0];
+#pragma unroll
+        for (int j = 1; j < W; j++) pre[j] = pre[j - 1] * d[j];
+        double r = m_rcp(pre[W - 1]);
+#pragma unroll
+        for (int j = W - 1; j >= 1; j--) {
+            const double inv = r * pre[j - 1];
+            r = r * d[j];
+            t[j] = copysign(fma(-2.0, inv, 1.0), z[j]);
+        }
+        t[0] = copysign(fma(-2.0, r, 1.0), z[0]);
+    }
+    // The operations, their order and their operands are those of eval_grad_pf<false> for D = 2, NV = 1.
+    template <class A>
+    __device__ static __forceinline__ void eval_grad_rw(cptr_t p, const RW& r, const RS& rs, const double (&c)[W],
+                                                        const double (&x)[NV], double wgt, A& acc, bool use_tab,
+                                                        const Exps* E1) {
+        static_assert(HAS_RW, "resident hidden layer");
+        p = launder(p);
+        double h[2][W], z[W];
+        CUDE_FENCE();
+        if (use_tab) {
+            m_tanh_from_exp<W>(E1->v, h[0]);
+        } else {
+            const SCol<W> col = ld_col<W>(p, 0);
+#pragma unroll
+            for (int j = 0; j < W; j++) z[j] = fma(col.v[j], x[0], c[j]);
+            act_tanh_vec<W, TT>(z, h[0]);
+        }
+        rw_for<0, 0, W>([&](auto i, auto j) {
+            if constexpr (i.value == 0) z[j.value] = rw_get<W * W + j.value>(r);
+            z[j.value] = rw_fma<W * i.value + j.value>(r, h[0][i.value], z[j.value]);
+        });
+        CUDE_FENCE();
+        rw_tanh(z, h[1]);
+        CUDE_FENCE();
+        double z0 = seed_from_sgpr(rs.bo), z1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            if (i & 1) z1 = fma(rs.wo.v[i], h[1][i], z1);
+            else z0 = fma(rs.wo.v[i], h[1][i], z0);
+        }
+        double sig;
+        act_softplus<TT>(z0 + z1, &sig);
+        const double dz = wgt * sig;
+        acc[G_OUT + W] += dz;
+        double dh[W], d[W];
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            acc[G_OUT + i] = fma(dz, h[1][i], acc[G_OUT + i]);
+            dh[i] = dz * rs.wo.v[i];
+        }
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            d[j] = dh[j] * fma(-h[1][j], h[1][j], 1.0);
+            acc[G_H + W * W + j] += d[j];
+        }
+        CUDE_FENCE();
+        double s[W][2];
+        rw_for<0, 0, W>([&](auto i, auto j) {
+            constexpr int ii = W - 1 - i.value, jj = j.value;
+            acc[G_H + jj + W * ii] = fma(d[jj], h[0][ii], acc[G_H + jj + W * ii]);
+            if constexpr (jj < 2) s[ii][jj] = 0.0;
+            s[ii][jj & 1] = rw_fma<W * ii + jj>(r, d[jj], s[ii][jj & 1]);
+            if constexpr (jj == W - 1) dh[ii] = s[ii][0] + s[ii][1];
+        });
+        CUDE_FENCE();
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            const double d1 = dh[j] * fma(-h[0][j], h[0][j], 1.0);
+            acc[G_C + j] += d1;
+            acc[G_W1V + j] = fma(d1, x[0], acc[G_W1V + j]);
+        }
+    }
+
     // value + weighted reverse sweep:  acc += wgt * d(out)/d(params);  if WANT_DX,
     // dx[i] += wgt * d(out)/dx_i.  Returns the network output.
     // PIN: hidden-layer accumulators pinned behind their update (default: the network's own rule, kPinLayers; the adaptive
@@ -1064,8 +1215,11 @@ struct MmProd {
     static constexpr bool HAS_TAB = false;          // one division per evaluation: nothing to tabulate
     static constexpr bool HAS_VW = false;
     static constexpr bool HAS_VW_SMALL = false;
+    static constexpr bool HAS_RW = false;
     static constexpr int DEPTH = 0, WIDTH = 1, NKEEP = 1;
     struct VW {};
+    struct RW {};
+    struct RS {};
     struct Exps {
         double v[1];
     };
