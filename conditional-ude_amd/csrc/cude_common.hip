@@ -595,6 +595,211 @@ hipError_t launch_fill(int64_t N, double v, double* out, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- per-subject profile-likelihood intervals (cude_profile_intervals; the numbered rule in include/cude.h): the scan's
+// SSE rows are reduced where they are, chunk by chunk, into a running per-subject state; sectioning rounds then tighten
+// both interval ends.  Every reduction is an exact minimum / maximum / integer sum combined in set order, so the state
+// depends neither on the decomposition nor on the chunk size.
+// Rule 1: every operation rounded on its own (no contraction), so that numpy's sse + pw * (x - pc) ** 2 has the same bits;
+// deliberately not fit_objective's fma form.  A non-finite F is above every threshold: +Inf.
+__device__ __forceinline__ double profile_objective(double sse, double x, double pw, double pc) {
+#pragma clang fp contract(off)
+    const double t = x - pc;
+    const double p = pw * (t * t);
+    const double f = sse + p;
+    return fabs(f) <= 1.79769313486231570815e308 ? f : __builtin_huge_val();
+}
+
+struct ProfilePartial {
+    double fmin;                // smallest F so far (+Inf: none finite yet) and its grid index (0 with none)
+    int32_t imin, first, last, cnt;     // first / last grid index with F <= thr (n_points / -1 with none), their count
+};
+__device__ __forceinline__ ProfilePartial profile_empty(int32_t n_points) {
+    return ProfilePartial{__builtin_huge_val(), 0, n_points, -1, 0};
+}
+// `b` covers later sets than `a`: strict <, the first minimum wins
+__device__ __forceinline__ void profile_combine(ProfilePartial& a, const ProfilePartial& b) {
+    if (b.fmin < a.fmin) { a.fmin = b.fmin; a.imin = b.imin; }
+    a.first = b.first < a.first ? b.first : a.first;
+    a.last = b.last > a.last ? b.last : a.last;
+    a.cnt += b.cnt;
+}
+
+// rule 2: objective at the centre, threshold, and the empty running state
+__global__ void profile_init_kernel(ProfileArgs a, const double* __restrict__ center, const double* __restrict__ sse_center,
+                                    double delta, const double* __restrict__ delta_i) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.N) return;
+    a.fmin[i] = __builtin_huge_val();
+    a.imin[i] = 0;
+    a.first[i] = a.n_points;
+    a.last[i] = -1;
+    a.cnt[i] = 0;
+    if (!a.thr) return;
+    const double fc = profile_objective(sse_center[i], center[i], a.pw, a.pc);
+    const double d = delta_i ? delta_i[i] : delta;
+    a.fcen[i] = fc;
+    a.thr[i] = fc < __builtin_huge_val() ? fc + d : __builtin_nan("");      // (failed centre: nothing compares <= NaN)
+}
+
+// rule 3: sets [k0, k0 + kn) of the scan, sse[k][i].  A workgroup is 64 subjects wide (one coalesced row segment per wave
+// and set) and kProfileWaves waves deep; wave w of workgroup row y reduces the `seg` consecutive sets from
+// (y * kProfileWaves + w) * seg on, the waves are combined in that order through LDS, and row y's result goes to partial
+// row y (profile_merge_kernel combines the rows, again in order).
+__global__ __launch_bounds__(64 * kProfileWaves) void profile_reduce_kernel(ProfileArgs a, int k0, int kn, int seg,
+                                                                            const double* __restrict__ sse) {
+    __shared__ double s_f[kProfileWaves][64];
+    __shared__ int32_t s_i[kProfileWaves][4][64];
+    const int lane = threadIdx.x, w = threadIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+    ProfilePartial p = profile_empty(a.n_points);
+    if (i < a.N) {
+        const int kb = ((int)blockIdx.y * kProfileWaves + w) * seg;
+        const int ke = kb + seg < kn ? kb + seg : kn;
+        const double thr = a.thr ? a.thr[i] : 0.0;
+        for (int k = kb; k < ke; k++) {
+            const double f = profile_objective(sse[(int64_t)k * a.N + i], a.values[k0 + k], a.pw, a.pc);
+            if (f < p.fmin) { p.fmin = f; p.imin = k0 + k; }
+            if (a.thr && f <= thr) {
+                if (p.cnt == 0) p.first = k0 + k;
+                p.last = k0 + k;
+                p.cnt++;
+            }
+        }
+    }
+    s_f[w][lane] = p.fmin;
+    s_i[w][0][lane] = p.imin; s_i[w][1][lane] = p.first; s_i[w][2][lane] = p.last; s_i[w][3][lane] = p.cnt;
+    __syncthreads();
+    if (w != 0 || i >= a.N) return;
+    for (int v = 1; v < kProfileWaves; v++)
+        profile_combine(p, ProfilePartial{s_f[v][lane], s_i[v][0][lane], s_i[v][1][lane], s_i[v][2][lane], s_i[v][3][lane]});
+    const int64_t r = (int64_t)blockIdx.y * a.N + i;
+    a.p_fmin[r] = p.fmin;
+    a.p_imin[r] = p.imin; a.p_first[r] = p.first; a.p_last[r] = p.last; a.p_cnt[r] = p.cnt;
+}
+
+// the chunk's `ny` partial rows, in order, behind the running state of the chunks before it
+__global__ void profile_merge_kernel(ProfileArgs a, int ny) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.N) return;
+    ProfilePartial p{a.fmin[i], a.imin[i], a.first[i], a.last[i], a.cnt[i]};
+    for (int y = 0; y < ny; y++) {
+        const int64_t r = (int64_t)y * a.N + i;
+        profile_combine(p, ProfilePartial{a.p_fmin[r], a.p_imin[r], a.p_first[r], a.p_last[r], a.p_cnt[r]});
+    }
+    a.fmin[i] = p.fmin;
+    a.imin[i] = p.imin; a.first[i] = p.first; a.last[i] = p.last; a.cnt[i] = p.cnt;
+}
+
+// rule 4: the grid's ends, the count and the status; a closed end gets its bracket (out = NaN marks an end the rounds
+// leave alone).  argmin[i] = values[imin[i]] in either form of the call.
+__global__ void profile_finish_kernel(ProfileArgs a, ProfileEnds e) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.N) return;
+    const double nan = __builtin_nan(""), inf = __builtin_huge_val();
+    e.argmin[i] = a.values[a.imin[i]];
+    if (!a.thr) return;
+    double lo_in = nan, lo_out = nan, hi_in = nan, hi_out = nan;
+    int32_t st = 0;
+    const int32_t first = a.first[i], last = a.last[i], cnt = a.cnt[i];
+    if (!(a.fcen[i] < inf)) {
+        st = kProfileCenterFailed;
+    } else if (cnt == 0) {
+        st = kProfileEmpty;
+    } else {
+        if (first == 0) { st |= kProfileLowerOpen; lo_in = -inf; }
+        else { lo_in = a.values[first]; lo_out = a.values[first - 1]; }
+        if (last == a.n_points - 1) { st |= kProfileUpperOpen; hi_in = inf; }
+        else { hi_in = a.values[last]; hi_out = a.values[last + 1]; }
+        if (cnt != last - first + 1) st |= kProfileDisconnected;
+    }
+    if (st != kProfileCenterFailed && a.fmin[i] < a.fcen[i]) st |= kProfileBelowCenter;
+    e.lo_in[i] = lo_in; e.lo_out[i] = lo_out; e.hi_in[i] = hi_in; e.hi_out[i] = hi_out;
+    e.status[i] = st;
+}
+
+// rule 5: p_j = out + (in - out) j / (m + 1), every operation rounded on its own (numpy's expression)
+__device__ __forceinline__ double profile_section(double out, double in, int j, int m) {
+#pragma clang fp contract(off)
+    const double t = (in - out) * (double)j;
+    return out + t / (double)(m + 1);
+}
+// candidates of one round: rows 0 ... m - 1 the lower end's p_1 ... p_m, rows m ... 2m - 1 the upper end's; an end without
+// a bracket rides along at the grid's argmin
+__global__ void profile_place_kernel(ProfileArgs a, ProfileEnds e, int m, double* __restrict__ cand) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.N) return;
+    const double dummy = e.argmin[i];
+    const double lo_out = e.lo_out[i], lo_in = e.lo_in[i], hi_out = e.hi_out[i], hi_in = e.hi_in[i];
+    for (int j = 1; j <= m; j++) {
+        cand[(int64_t)(j - 1) * a.N + i] = lo_out == lo_out ? profile_section(lo_out, lo_in, j, m) : dummy;
+        cand[(int64_t)(m + j - 1) * a.N + i] = hi_out == hi_out ? profile_section(hi_out, hi_in, j, m) : dummy;
+    }
+}
+// the new bracket of one end from its m rows: in = the p_j nearest to `out` with F <= thr (none: in stays), out = that
+// point's neighbour on the out side -- the outermost crossing is kept
+__device__ __forceinline__ void profile_resolve_end(const ProfileArgs& a, int64_t i, int m, const double* __restrict__ cand,
+                                                    const double* __restrict__ sse, double thr, double* out_p, double* in_p) {
+    double out = out_p[i];
+    if (!(out == out)) return;
+    for (int j = 0; j < m; j++) {
+        const double x = cand[(int64_t)j * a.N + i];
+        if (profile_objective(sse[(int64_t)j * a.N + i], x, a.pw, a.pc) <= thr) {
+            in_p[i] = x;
+            break;
+        }
+        out = x;
+    }
+    out_p[i] = out;
+}
+__global__ void profile_resolve_kernel(ProfileArgs a, ProfileEnds e, int m, const double* __restrict__ cand,
+                                       const double* __restrict__ sse) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.N) return;
+    const double thr = a.thr[i];
+    profile_resolve_end(a, i, m, cand, sse, thr, e.lo_out, e.lo_in);
+    profile_resolve_end(a, i, m, cand + (int64_t)m * a.N, sse + (int64_t)m * a.N, thr, e.hi_out, e.hi_in);
+}
+
+hipError_t launch_profile_init(const ProfileArgs& a, const double* center, const double* sse_center, double delta,
+                               const double* delta_i, hipStream_t s) {
+    const int bs = 256;
+    hipLaunchKernelGGL(profile_init_kernel, dim3((unsigned)((a.N + bs - 1) / bs)), dim3(bs), 0, s, a, center, sse_center,
+                       delta, delta_i);
+    return hipGetLastError();
+}
+int profile_reduce_rows(int64_t N, int kn) {
+    const int64_t nbx = (N + 63) / 64;
+    if (nbx >= 1024) return 1;                                 // the subjects alone fill the chip
+    const int64_t by_sets = (kn + kProfileWaves * 8 - 1) / (kProfileWaves * 8);      // >= 8 sets per wave
+    return (int)std::max<int64_t>(1, std::min<int64_t>(by_sets, (2048 + nbx - 1) / nbx));
+}
+hipError_t launch_profile_reduce(const ProfileArgs& a, int k0, int kn, const double* sse, hipStream_t s) {
+    if (kn < 1) return hipErrorInvalidValue;
+    const int ny = profile_reduce_rows(a.N, kn);
+    const int seg = (kn + ny * kProfileWaves - 1) / (ny * kProfileWaves);
+    hipLaunchKernelGGL(profile_reduce_kernel, dim3((unsigned)((a.N + 63) / 64), (unsigned)ny), dim3(64, kProfileWaves), 0, s,
+                       a, k0, kn, seg, sse);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int bs = 256;
+    hipLaunchKernelGGL(profile_merge_kernel, dim3((unsigned)((a.N + bs - 1) / bs)), dim3(bs), 0, s, a, ny);
+    return hipGetLastError();
+}
+hipError_t launch_profile_finish(const ProfileArgs& a, const ProfileEnds& e, hipStream_t s) {
+    const int bs = 256;
+    hipLaunchKernelGGL(profile_finish_kernel, dim3((unsigned)((a.N + bs - 1) / bs)), dim3(bs), 0, s, a, e);
+    return hipGetLastError();
+}
+hipError_t launch_profile_round(const ProfileArgs& a, const ProfileEnds& e, int m, int resolve, double* cand, const double* sse,
+                                hipStream_t s) {
+    if (m < 1 || m > kProfileMaxSections) return hipErrorInvalidValue;
+    const int bs = 256;
+    const dim3 grid((unsigned)((a.N + bs - 1) / bs));
+    if (resolve) hipLaunchKernelGGL(profile_resolve_kernel, grid, dim3(bs), 0, s, a, e, m, cand, sse);
+    else hipLaunchKernelGGL(profile_place_kernel, grid, dim3(bs), 0, s, a, e, m, cand);
+    return hipGetLastError();
+}
+
 // Adam exactly as Optimisers.jl: m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
 // x -= lr * (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps).  Skipped when any subject failed
 // (g_nn[P+1] > 0): the reference's optimiser would see an Inf objective there.

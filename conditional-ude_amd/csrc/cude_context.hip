@@ -208,6 +208,7 @@ const OptionEntry kOptions[] = {
     {"dense_chunk", "CUDE_DENSE_CHUNK", &Options::dense_chunk, false, false},
     {"dense_layout", "CUDE_DENSE_LAYOUT", &Options::dense_layout, false, false},
     {"refine_fused", "CUDE_REFINE_FUSED", &Options::refine_fused, false, false},
+    {"profile_chunk", "CUDE_PROFILE_CHUNK", &Options::profile_chunk, false, false},
 };
 }  // namespace
 

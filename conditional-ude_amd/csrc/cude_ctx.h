@@ -89,6 +89,8 @@ struct Options {
                                 //   [3 x T x N] (0, measured faster: cude_simulate) or lane-contiguous [T][3][N] + a transpose (1)
     int refine_fused = 1;       // "refine_fused" / CUDE_REFINE_FUSED: cude_refine_conditional in fixed-step mode as ONE launch (1) or as one
                                 //   tangent launch + one update launch per evaluation (0: the form the adaptive mode always runs)
+    int profile_chunk = 0;      // "profile_chunk" / CUDE_PROFILE_CHUNK: grid points per launch of cude_profile_conditional / cude_profile_intervals
+                                //   (0 = as many as ~512 MB of scratch allow; tests force several launches with it)
     // ("hidden_activation" = tanh | relu | sigmoid, "output_activation" = softplus | identity: kept in cude_ctx::net)
     // ---- ablation
     int mixed = 1;              // CUDE_NO_MIXED

@@ -482,6 +482,36 @@ hipError_t launch_supp_refine(const NetShape& net, const SuppArgs& a, const Refi
 // phase 0 = clamp the starts, 1 = the rule's update behind an evaluation at xt (both: stepped form); 2 = objective at the
 // result from the SSE in r.sse (either form)
 hipError_t launch_refine_step(int phase, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
+// per-subject profile-likelihood intervals (cude_profile_intervals, cude_common.hip): the scan's running state, the ends'
+// brackets and the CUDE_CI_* bits of include/cude.h; all arrays [N] unless noted
+constexpr int kProfileWaves = 4;                  // waves of a reduction workgroup: the set dimension is split over them
+constexpr int kProfileMaxSections = 16;
+constexpr int32_t kProfileLowerOpen = 1, kProfileUpperOpen = 2, kProfileDisconnected = 4, kProfileEmpty = 8,
+                  kProfileCenterFailed = 16, kProfileBelowCenter = 32;
+struct ProfileArgs {
+    int64_t N;
+    int32_t n_points;
+    double pw, pc;                                // penalty pw (x - pc)^2
+    const double* values;                         // [n_points]
+    double* thr; double* fcen;                    // threshold and objective at the centre; thr null: minimum and argmin only
+    double* fmin; int32_t* imin; int32_t* first; int32_t* last; int32_t* cnt;     // running state of the scan
+    double* p_fmin; int32_t* p_imin; int32_t* p_first; int32_t* p_last; int32_t* p_cnt;   // [rows][N] of one chunk's reduction
+};
+struct ProfileEnds {
+    double* lo_out; double* lo_in; double* hi_in; double* hi_out;      // out = NaN: no bracket (open, empty, failed)
+    double* argmin;
+    int32_t* status;
+};
+// centre objective, threshold (delta_i [N] or null: delta) and the empty running state
+hipError_t launch_profile_init(const ProfileArgs& a, const double* center, const double* sse_center, double delta,
+                               const double* delta_i, hipStream_t s);
+// sets [k0, k0 + kn) of the scan (sse [kn][N]) into the running state; profile_reduce_rows: partial rows it needs
+int profile_reduce_rows(int64_t N, int kn);
+hipError_t launch_profile_reduce(const ProfileArgs& a, int k0, int kn, const double* sse, hipStream_t s);
+hipError_t launch_profile_finish(const ProfileArgs& a, const ProfileEnds& e, hipStream_t s);
+// one sectioning round with m interior points per end: resolve = 0 places the 2m candidates [2m][N], 1 moves the brackets
+hipError_t launch_profile_round(const ProfileArgs& a, const ProfileEnds& e, int m, int resolve, double* cand, const double* sse,
+                                hipStream_t s);
 hipError_t launch_fill(int64_t N, double v, double* out, hipStream_t s);
 hipError_t launch_fill_rows(int64_t N, int n_rows, const double* values, double* out, hipStream_t s);
 // population preparation

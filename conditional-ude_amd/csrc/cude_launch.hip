@@ -866,6 +866,15 @@ int32_t forward_sets(cude_ctx* c, const SetsForward& s) {
     if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
     return CUDE_OK;
 }
+
+// Grid points per launch of a likelihood-profile scan (cude_profile_conditional, cude_profile_intervals): the grid's y
+// dimension and ~512 MB of scratch (conditional sets, SSEs, partial rows); option "profile_chunk" > 0 lowers it.
+int64_t profile_chunk_sets(cude_ctx* c, int64_t n_points) {
+    const double per_point = 8.0 * (2.0 * c->N + (double)c->nblocks * (c->P + 2));
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_points, 32768), (int64_t)(512e6 / per_point)));
+    if (c->opt.profile_chunk > 0) chunk = std::min<int64_t>(chunk, c->opt.profile_chunk);
+    return chunk;
+}
 }  // namespace
 
 extern "C" {
@@ -1236,11 +1245,8 @@ int32_t cude_profile_conditional(cude_ctx* c, int32_t n_points, const double* va
     if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
     if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
     if (n_points < 1 || !values || !sse_out) return fail(CUDE_ERR_ARG, "null/empty input");
-    const int P = c->P;
-    const int64_t N = c->N, nb = c->nblocks;
-    // grid points per launch: the grid's y dimension and ~512 MB of scratch (conditional sets, SSEs, partial rows)
-    const double per_point = 8.0 * (2.0 * N + (double)nb * (P + 2));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_points, 32768), (int64_t)(512e6 / per_point)));
+    const int64_t N = c->N;
+    const int64_t chunk = profile_chunk_sets(c, n_points);
     DevBuf<double> d_val, d_cond, d_sse, d_part;
     HIP_TRY(d_val.resize((size_t)chunk));
     HIP_TRY(d_cond.resize((size_t)chunk * N));
@@ -1256,6 +1262,120 @@ int32_t cude_profile_conditional(cude_ctx* c, int32_t n_points, const double* va
         if ((rc = forward_sets(c, fwd))) return rc;
         HIP_TRY(hipMemcpyAsync(sse_out + k0 * N, d_sse.p, kn * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return CUDE_OK;
+}
+
+int32_t cude_profile_intervals(cude_ctx* c, int32_t n_points, const double* values, const double* center, double delta,
+                               const double* delta_per_subject, double penalty_weight, double penalty_center,
+                               int32_t n_rounds, int32_t n_sections, double* lower_out, double* upper_out,
+                               double* argmin_out, double* min_out, double* center_objective_out, int32_t* n_inside_out,
+                               int32_t* status_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_profile_intervals under stream capture");
+    if (n_points < 2 || !values) return fail(CUDE_ERR_ARG, "need n_points >= 2 and the scan values");
+    for (int32_t k = 0; k < n_points; k++)
+        if (!std::isfinite(values[k]) || (k > 0 && !(values[k] > values[k - 1])))
+            return fail(CUDE_ERR_ARG, "the scan values must be finite and strictly increasing");
+    if (n_rounds < 0 || n_rounds > 64 || n_sections < 1 || n_sections > cude::kProfileMaxSections)
+        return fail(CUDE_ERR_ARG, "need 0 <= n_rounds <= 64 and 1 <= n_sections <= 16");
+    if (!(penalty_weight >= 0) || !std::isfinite(penalty_weight) || !std::isfinite(penalty_center))
+        return fail(CUDE_ERR_ARG, "need a finite penalty_weight >= 0 and a finite penalty_center");
+    // rule 6: with the minimum and its place alone asked for there is no centre and no threshold
+    const bool intervals = lower_out || upper_out || center_objective_out || n_inside_out || status_out;
+    if (!intervals && !argmin_out && !min_out) return fail(CUDE_ERR_ARG, "no output requested");
+    const int64_t N = c->N;
+    if (intervals) {
+        if (!center && !c->have_cond) return fail(CUDE_ERR_STATE, "no centre: conditional parameters not set and center is null");
+        if (delta_per_subject) {
+            for (int64_t i = 0; i < N; i++)
+                if (!(delta_per_subject[i] >= 0)) return fail(CUDE_ERR_ARG, "delta_per_subject must be >= 0 (may be +Inf)");
+        } else if (!(delta >= 0)) {
+            return fail(CUDE_ERR_ARG, "delta must be >= 0 (may be +Inf)");
+        }
+    }
+    const int m = n_sections, rounds = intervals ? n_rounds : 0;
+    const int64_t chunk = profile_chunk_sets(c, n_points);
+    const int64_t max_sets = std::max<int64_t>(chunk, rounds > 0 ? 2 * m : 1);
+    const int rows = cude::profile_reduce_rows(N, (int)chunk);
+    // device scratch: one chunk of conditional sets and SSEs, the reduction's partial rows and 9 + 5 numbers per subject
+    DevBuf<double> d_val, d_cond, d_sse, d_part, d_state, d_pf;
+    DevBuf<int32_t> d_istate, d_pi;
+    HIP_TRY(d_val.resize((size_t)n_points));
+    HIP_TRY(d_cond.resize((size_t)max_sets * N));
+    HIP_TRY(d_sse.resize((size_t)max_sets * N));
+    HIP_TRY(d_state.resize((size_t)11 * N));              // thr, fcen, fmin, lo_out, lo_in, hi_in, hi_out, argmin, centre, sse_c, delta
+    HIP_TRY(d_istate.resize((size_t)5 * N));              // imin, first, last, cnt, status
+    HIP_TRY(d_pf.resize((size_t)rows * N));
+    HIP_TRY(d_pi.resize((size_t)4 * rows * N));
+    if ((rc = reserve_sets_forward(c, max_sets, false, d_part))) return rc;
+    double* q = d_state.p;
+    cude::ProfileArgs a{};
+    a.N = N; a.n_points = n_points; a.pw = penalty_weight; a.pc = penalty_center; a.values = d_val.p;
+    a.thr = intervals ? q : nullptr; a.fcen = q + N; a.fmin = q + 2 * N;
+    a.imin = d_istate.p; a.first = d_istate.p + N; a.last = d_istate.p + 2 * N; a.cnt = d_istate.p + 3 * N;
+    a.p_fmin = d_pf.p;
+    a.p_imin = d_pi.p; a.p_first = d_pi.p + (size_t)rows * N; a.p_last = d_pi.p + (size_t)2 * rows * N;
+    a.p_cnt = d_pi.p + (size_t)3 * rows * N;
+    cude::ProfileEnds e{};
+    e.lo_out = q + 3 * N; e.lo_in = q + 4 * N; e.hi_in = q + 5 * N; e.hi_out = q + 6 * N; e.argmin = q + 7 * N;
+    e.status = d_istate.p + 4 * N;
+    double* d_center = q + 8 * N;
+    double* d_sse_c = q + 9 * N;
+    double* d_delta = q + 10 * N;
+    HIP_TRY(hipMemcpyAsync(d_val.p, values, (size_t)n_points * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const double* cen = nullptr;
+    if (intervals) {                                      // rule 2: the centre, in one forward launch (cude_forward's own)
+        cen = c->cond.p;
+        if (center) {
+            HIP_TRY(hipMemcpyAsync(d_center, center, N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            cen = d_center;
+        }
+        if (delta_per_subject)
+            HIP_TRY(hipMemcpyAsync(d_delta, delta_per_subject, N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if ((rc = run_ensemble(c, false, nullptr, true, cen, d_sse_c))) return rc;
+    }
+    HIP_TRY(cude::launch_profile_init(a, cen, d_sse_c, delta, delta_per_subject ? d_delta : nullptr, c->stream));
+    SetsForward fwd;                                      // one network, kn grid values
+    fwd.cond = d_cond.p; fwd.nn = c->nn.p; fwd.sse = d_sse.p; fwd.partials = d_part.p;
+    for (int64_t k0 = 0; k0 < n_points; k0 += chunk) {    // rule 3: the scan, every chunk reduced where it is
+        const int64_t kn = std::min<int64_t>(chunk, n_points - k0);
+        HIP_TRY(cude::launch_fill_rows(N, (int)kn, d_val.p + k0, d_cond.p, c->stream));
+        fwd.n_sets = (int)kn;
+        if ((rc = forward_sets(c, fwd))) return rc;
+        HIP_TRY(cude::launch_profile_reduce(a, (int)k0, (int)kn, d_sse.p, c->stream));
+        if (k0 == 0 && (rc = maybe_regroup(c))) return rc; // (adaptive mode: the first launch has told the step counts)
+    }
+    HIP_TRY(cude::launch_profile_finish(a, e, c->stream));   // rule 4
+    for (int r = 0; r < rounds; r++) {                    // rule 5: both ends of every subject, 2m sets per launch
+        HIP_TRY(cude::launch_profile_round(a, e, m, 0, d_cond.p, d_sse.p, c->stream));
+        fwd.n_sets = 2 * m;
+        if ((rc = forward_sets(c, fwd))) return rc;
+        HIP_TRY(cude::launch_profile_round(a, e, m, 1, d_cond.p, d_sse.p, c->stream));
+    }
+    std::vector<int32_t> status;
+    const auto back = [&](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIP_TRY(back(lower_out, e.lo_in, N * sizeof(double)));
+    HIP_TRY(back(upper_out, e.hi_in, N * sizeof(double)));
+    HIP_TRY(back(argmin_out, e.argmin, N * sizeof(double)));
+    HIP_TRY(back(min_out, a.fmin, N * sizeof(double)));
+    HIP_TRY(back(center_objective_out, a.fcen, N * sizeof(double)));
+    HIP_TRY(back(n_inside_out, a.cnt, N * sizeof(int32_t)));
+    if (intervals) {
+        status.resize((size_t)N);
+        HIP_TRY(back(status.data(), e.status, N * sizeof(int32_t)));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (intervals) {                                      // failed centres are what cude_n_failed counts
+        int64_t failed = 0;
+        for (int64_t i = 0; i < N; i++) failed += (status[(size_t)i] & CUDE_CI_CENTER_FAILED) != 0;
+        c->last_failed = failed;
+        if (status_out) std::memcpy(status_out, status.data(), (size_t)N * sizeof(int32_t));
     }
     return CUDE_OK;
 }

@@ -72,6 +72,9 @@ _SIGNATURES = {
     "cude_refine_conditional": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_double,
                                             C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cude_profile_intervals": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_double,
+                                           C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cude_mh_chain": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "cude_n_failed": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),

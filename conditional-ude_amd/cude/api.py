@@ -878,6 +878,44 @@ def likelihood_profiles(betas, neural_network_parameters, models, timepoints, cp
     return nll, nll_min, values
 
 
+def _profile_intervals(eng, center, values, sigma, target, rounds, sections, return_details):
+    """Intervals of every subject of `eng` at the threshold of `target`: the reference's nll <= nll_min + Delta with
+    nll = SSE / (2 sigma^2) is SSE <= SSE(centre) + 2 sigma^2 Delta, which is what the device compares."""
+    sig = np.asarray(sigma, dtype=np.float64)
+    d = 2.0 * sig ** 2 * _CI_THRESHOLDS.get(target, _CI_THRESHOLDS["raue95"])
+    r = eng.profile_intervals(values, center, float(d) if d.ndim == 0 else 0.0,
+                              delta_per_subject=None if d.ndim == 0 else d.reshape(-1), rounds=rounds, sections=sections)
+    cis = [(float(lo), float(hi)) for lo, hi in zip(r["lower"], r["upper"])]
+    return (cis, r) if return_details else cis
+
+
+def profile_confidence_intervals(betas, neural_network_parameters, models, timepoints, cpeptide_data, lower_bound,
+                                 upper_bound, sigma, *, steps=1000, target="cantelli95", rounds=0, sections=3,
+                                 n_steps=None, return_details=False):
+    """The loop `find_confidence_intervals(likelihood_profile(...)...; target)` over all subjects
+    (src/likelihood-profiles.jl:34-59 on the profiles of c-peptide/02-conditional.jl:186-188) with the profiles kept on
+    the device (cude_profile_intervals): a list of (lower, upper) per subject, -/+Inf where the interval reaches an end of
+    [lower_bound, upper_bound], (nan, nan) where no profile point lies within the threshold (the reference raises there)
+    or the solve at betas[i] failed.  rounds = 0: find_confidence_intervals on row i of likelihood_profiles (up to a
+    tie to rounding between nll and SSE units).  rounds > 0: every closed end is then tightened by `rounds` sectioning
+    rounds of `sections` interior points, to (upper_bound - lower_bound) / (steps - 1) / (sections + 1) ** rounds; the
+    ends reported lie inside the threshold.  sigma: scalar or (N,).  An unknown target falls back to raue95, as the
+    reference does.  A list of CPeptideODEModel profiles the raw k, as `sensitivities` does.  return_details: also the
+    dict of Engine.profile_intervals (argmin, min, center_objective, n_inside, status)."""
+    if _is_model(models):
+        models, cpeptide_data = [models], np.asarray(cpeptide_data)[None, :]
+    center = np.asarray(betas, dtype=np.float64).reshape(-1)
+    if isinstance(models[0], CPeptideODEModel):
+        pop = _population(models, timepoints, cpeptide_data, n_steps, cond_space="raw")
+        nn = pop.shared if neural_network_parameters is None else neural_network_parameters
+    else:
+        pop = _population(models, timepoints, cpeptide_data, n_steps)
+        nn = neural_network_parameters
+    pop.engine.set_params(nn, None)
+    return _profile_intervals(pop.engine, center[:pop.N], np.linspace(lower_bound, upper_bound, steps), sigma, target,
+                              rounds, sections, return_details)
+
+
 # ----------------------------------------------------------------------------- sensitivities, Fisher information
 def sensitivities(theta, args, *, n_steps=None):
     """Output sensitivities of every subject to its own conditional parameter, by the library's tangent-linear solve
@@ -1033,6 +1071,17 @@ def suppression_sensitivities(p, args, *, n_steps=None):
     pop.engine.set_params(p.neural, p.theta)
     out = pop.engine.sensitivity()
     return out["sens"], out["info"], out["score"], out["sse"]
+
+
+def suppression_profile_intervals(p, args, lower_bound, upper_bound, sigma, *, steps=1000, target="cantelli95", rounds=0,
+                                  sections=3, n_steps=None, return_details=False):
+    """profile_confidence_intervals for the suppression model: args = (prob, individual_data, timepoints, lambda) as
+    suppression_loss, centres p.theta, network p.neural; the profiled objective is the per-subject weighted SSE."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, None)
+    return _profile_intervals(pop.engine, np.asarray(p.theta, dtype=np.float64).reshape(-1),
+                              np.linspace(lower_bound, upper_bound, steps), sigma, target, rounds, sections, return_details)
 
 
 def suppression_loss_and_gradient(p, args, *, n_steps=None):

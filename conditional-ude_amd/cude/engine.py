@@ -59,6 +59,8 @@ _REDUCE = C.CFUNCTYPE(C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.
 
 # status codes of Engine.refine_conditional (CUDE_REFINE_* of include/cude.h)
 REFINE_CONVERGED, REFINE_AT_BOUND, REFINE_MAX_EVALS, REFINE_FLAT, REFINE_FAILED = range(5)
+# status bits of Engine.profile_intervals (CUDE_CI_* of include/cude.h)
+CI_LOWER_OPEN, CI_UPPER_OPEN, CI_DISCONNECTED, CI_EMPTY, CI_CENTER_FAILED, CI_BELOW_CENTER = 1, 2, 4, 8, 16, 32
 
 
 def lbfgs_minimize_sharded(fg, x0, n_shared, reduce, maxiters=1000):
@@ -373,6 +375,27 @@ class Engine:
         v = _f64(values).reshape(-1)
         out = np.empty((v.size, self.N))
         check(self._lib.cude_profile_conditional(self._h, v.size, _ptr(v), _ptr(out)))
+        return out
+
+    def profile_intervals(self, values, center=None, delta=0.0, *, delta_per_subject=None, penalty_weight=0.0,
+                          penalty_center=0.0, rounds=0, sections=3, argmin_only=False):
+        """Per-subject profile-likelihood intervals with the profile kept on the device (cude_profile_intervals): the scan
+        over `values` (K,) is reduced there chunk by chunk, `rounds` sectioning rounds with `sections` interior points
+        per end then tighten both ends.  center (N,) -- None: the context's conditional parameters; the threshold of
+        subject i is F_i(center_i) + delta (or delta_per_subject[i]), in SSE units.  Returns dict(lower, upper, argmin,
+        min, center_objective (N,) doubles; n_inside, status (N,) int32, status = CI_* bits).  argmin_only: dict(argmin,
+        min) of the scan alone -- no centre solve, no threshold."""
+        v = _f64(values).reshape(-1)
+        cen = None if center is None else np.ascontiguousarray(np.broadcast_to(_f64(center), (self.N,)))
+        dps = None if delta_per_subject is None else np.ascontiguousarray(np.broadcast_to(_f64(delta_per_subject), (self.N,)))
+        out = {k: np.empty(self.N) for k in (("argmin", "min") if argmin_only else
+                                             ("lower", "upper", "argmin", "min", "center_objective"))}
+        if not argmin_only:
+            out["n_inside"], out["status"] = np.empty(self.N, dtype=np.int32), np.empty(self.N, dtype=np.int32)
+        check(self._lib.cude_profile_intervals(
+            self._h, v.size, _ptr(v), _ptr(cen), float(delta), _ptr(dps), float(penalty_weight), float(penalty_center),
+            int(rounds), int(sections), _ptr(out.get("lower")), _ptr(out.get("upper")), _ptr(out["argmin"]),
+            _ptr(out["min"]), _ptr(out.get("center_objective")), _ptr(out.get("n_inside")), _ptr(out.get("status"))))
         return out
 
     def fit_conditional(self, lower, upper, n_grid=41, n_iters=48, penalty_weight=0.0, penalty_center=0.0):

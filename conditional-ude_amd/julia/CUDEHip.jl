@@ -26,6 +26,7 @@ using Statistics: mean, var
 export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEModel, CPeptideConditionalCovariateUDEModel,
        CPeptideUDEModel,
        loss, loss_sigma, loss_and_gradient!, train, train_with_sigma, evaluate_model, likelihood_profile,
+       profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals
 
@@ -249,6 +250,26 @@ function profile_conditional(c::Ctx, values::Vector{Float64})
     GC.@preserve values sse check(ccall((:cude_profile_conditional, LIB), Int32,
         (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), c.h, length(values), values, sse))
     sse
+end
+
+# per-subject profile-likelihood intervals with the profile kept on the device (cude_profile_intervals): the scan over
+# `values` reduced there chunk by chunk, then `rounds` sectioning rounds of `sections` interior points per end; center =
+# nothing: the context's conditional parameters; the threshold of subject i is Fᵢ(centerᵢ) + delta (delta_per_subject[i]),
+# in SSE units.  Returns (lower, upper, argmin, min, center_objective, n_inside, status = CI_* bits)
+const CI_LOWER_OPEN, CI_UPPER_OPEN, CI_DISCONNECTED, CI_EMPTY, CI_CENTER_FAILED, CI_BELOW_CENTER = 1, 2, 4, 8, 16, 32
+function profile_intervals(c::Ctx, values::Vector{Float64}, center, delta; delta_per_subject = nothing, penalty_weight = 0.0,
+                           penalty_center = 0.0, rounds = 0, sections = 3)
+    lower = Vector{Float64}(undef, c.N); upper = similar(lower); amin = similar(lower); fmin = similar(lower)
+    fcen = similar(lower)
+    n_inside = Vector{Int32}(undef, c.N); status = Vector{Int32}(undef, c.N)
+    cen = center === nothing ? nothing : Vector{Float64}(vec(center))
+    dps = delta_per_subject === nothing ? nothing : Vector{Float64}(vec(delta_per_subject))
+    GC.@preserve values cen dps lower upper amin fmin fcen n_inside status check(ccall((:cude_profile_intervals, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Float64, Float64, Int32, Int32, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+        c.h, length(values), values, cen === nothing ? C_NULL : pointer(cen), delta, dps === nothing ? C_NULL : pointer(dps),
+        penalty_weight, penalty_center, rounds, sections, lower, upper, amin, fmin, fcen, n_inside, status))
+    lower, upper, amin, fmin, fcen, n_inside, status
 end
 
 adam_init!(c::Ctx, η; β1 = 0.9, β2 = 0.999, ϵ = 1e-8) =
@@ -839,6 +860,26 @@ function likelihood_profile(β, neural_network_parameters, model::CPeptideCondit
     parameter_values = range(lower_bound, stop = upper_bound, length = steps)
     nll_values = vec(profile_conditional(c, collect(Float64, parameter_values))) ./ (2 * sigma^2)
     nll_values, nll_minimum, parameter_values
+end
+
+# find_confidence_intervals (src/likelihood-profiles.jl:34-59) over the likelihood profiles of ALL subjects
+# (c-peptide/02-conditional.jl:186-188) without the profiles leaving the device: one (lower, upper) pair per subject, ∓Inf
+# where the interval reaches an end of the profiled range, (NaN, NaN) where no profile point lies within the threshold.
+# rounds = 0: the reference's answer on `steps` points; rounds > 0: every closed end tightened by sectioning to
+# (upper_bound - lower_bound) / (steps - 1) / (sections + 1)^rounds.  sigma: scalar or one per subject.
+const CI_THRESHOLDS = Dict("cantelli95" => 7.16, "cantelli90" => 5.24, "raue95" => 3.841458820694124)
+function profile_confidence_intervals(betas, neural_network_parameters, models, timepoints, cpeptide_data, lower_bound,
+                                      upper_bound, sigma; steps = 1000, target = "cantelli95", rounds = 0,
+                                      sections = 3, n_steps = nothing, return_details = false)
+    c = population(models, timepoints, cpeptide_data; n_steps = n_steps)
+    set_params!(c, neural_network_parameters, nothing)
+    Δ = get(CI_THRESHOLDS, target, CI_THRESHOLDS["raue95"])
+    d = 2 .* sigma .^ 2 .* Δ
+    values = collect(Float64, range(lower_bound, stop = upper_bound, length = steps))
+    r = profile_intervals(c, values, betas, d isa Real ? Float64(d) : 0.0; delta_per_subject = d isa Real ? nothing : d,
+                          rounds = rounds, sections = sections)
+    cis = collect(zip(r[1], r[2]))
+    return_details ? (cis, r) : cis
 end
 
 # ----------------------------------------------------------------------------------------------- sensitivities

@@ -331,6 +331,53 @@ int32_t cude_refine_conditional(cude_ctx* ctx, const double* x0, double lower, d
                                 double* cond_out, double* objective_out, double* sse_out, double* info_out,
                                 int32_t* evals_out, int32_t* status_out);
 
+/* Per-subject profile-likelihood intervals with the whole profile kept on the device -- the loop around
+ * `find_confidence_intervals(loss_values, loss_minimum, parameter_values; target)` (src/likelihood-profiles.jl:34-59, run
+ * for every subject over 1000-10000 profile points at c-peptide/02-conditional.jl:186-188).  The host receives a handful
+ * of numbers per subject, never the n_points x N profile.
+ *   1. Objective: F_i(x) = SSE_i(x) + pw (x - pc)^2 with the shared parameters frozen at the context's, every operation
+ *      rounded on its own: t = x - pc; p = pw (t t); F = SSE + p (no fma contraction: numpy's sse + pw * (x - pc) ** 2
+ *      has the same bits; deliberately not cude_fit_conditional's fma form).  A non-finite F is above every threshold.
+ *   2. Centre and threshold: center[N] (NULL: the context's conditional parameters) is evaluated once, in one forward
+ *      launch (cude_forward's); thr_i = F_i(center_i) + d_i, d_i = delta_per_subject[i] if given, else delta, in SSE
+ *      units (the mirrors pass 2 sigma^2 Delta, Delta = 7.16 / 5.24 / chi^2_1(0.95)); d_i >= 0, +Inf allowed.
+ *   3. Scan: values[n_points] strictly increasing and finite; every subject at every value as the parameter sets of
+ *      cude_profile_conditional's launches (the same SSE bits; option "profile_chunk" = sets per launch).  Every chunk is
+ *      reduced on the device into a running per-subject state: the minimum of F and its grid index (strict <: the first
+ *      minimum wins; no finite value: index 0, minimum +Inf), the first and the last index with F <= thr, their count.
+ *      All of these are exact, so the result depends neither on the chunk size nor on how a chunk is split.
+ *   4. Grid result (n_rounds = 0, the reference's answer exactly): lower = values[first], or -Inf if first == 0;
+ *      upper = values[last], or +Inf if last == n_points - 1.
+ *   5. Refinement: n_rounds rounds (0 ... 64) with n_sections = m interior points per end (1 ... 16; 1 = bisection).  A
+ *      closed end has the bracket (out, in) = (values[first - 1], values[first]) / (values[last + 1], values[last]).  A
+ *      round evaluates p_j = out + (in - out) j / (m + 1), j = 1 ... m, of both ends in ONE forward launch of 2m sets; the
+ *      new `in` is the p_j nearest to `out` with F <= thr (none: `in` stays), the new `out` that point's neighbour on the
+ *      out side, so the outermost crossing is kept (as the reference keeps the outermost grid point) and the bracket
+ *      shrinks by m + 1 per round.  Open, empty and failed ends ride along at a dummy point and are not written.  The
+ *      reported ends are the `in` points: they lie inside the threshold.  All rounds are queued; one synchronisation.
+ *   6. Outputs, all [N], all optional, at least one: lower_out, upper_out, argmin_out (= values[index of the minimum]),
+ *      min_out, center_objective_out (+Inf for a failed centre), n_inside_out (rule 3's count), status_out (CUDE_CI_*
+ *      bits).  With argmin_out / min_out alone the centre solve and the rounds are skipped and nothing is compared to a
+ *      threshold.
+ *   7. Fixed-step and adaptive mode (adaptive: large populations are re-ordered after the first chunk as in
+ *      cude_fit_conditional; cude_adaptive_steps refuses afterwards), both network models, the symbolic model in either
+ *      cond_space, the fallback kernel.  A sharded population needs no exchange: every output is per subject.
+ *   8. CUDE_ERR_ARG: values not increasing / not finite, n_points < 2, n_sections or n_rounds out of range, a negative
+ *      or NaN d_i, no output; CUDE_ERR_STATE: population or shared parameters (or, with center NULL, conditional
+ *      parameters) not set, stream capture.
+ * Leaves the context's parameters untouched. */
+#define CUDE_CI_LOWER_OPEN     1  /* the in-threshold set reaches values[0]: lower = -Inf (reference :55) */
+#define CUDE_CI_UPPER_OPEN     2  /* ... reaches values[n_points-1]: upper = +Inf (:56) */
+#define CUDE_CI_DISCONNECTED   4  /* grid points above the threshold lie between the outermost ones inside it */
+#define CUDE_CI_EMPTY          8  /* no grid point within the threshold: lower = upper = NaN */
+#define CUDE_CI_CENTER_FAILED 16  /* objective at the centre not finite: lower = upper = NaN; counted by cude_n_failed */
+#define CUDE_CI_BELOW_CENTER  32  /* some grid point has a smaller objective than the centre: the centre is no minimiser */
+int32_t cude_profile_intervals(cude_ctx* ctx, int32_t n_points, const double* values, const double* center,
+                               double delta, const double* delta_per_subject, double penalty_weight,
+                               double penalty_center, int32_t n_rounds, int32_t n_sections,
+                               double* lower_out, double* upper_out, double* argmin_out, double* min_out,
+                               double* center_objective_out, int32_t* n_inside_out, int32_t* status_out);
+
 /* SAEM E-step on the device: n_mc Metropolis-Hastings steps of every subject's conditional parameter
  * (`mcmc_step` src/saem.jl:86-108, applied n_mcmc_steps times with the stochastic-approximation update of the
  * chain state :177-186).  The chain state is the context's conditional parameters (updated in place); the
@@ -508,9 +555,10 @@ int32_t cude_xchg_info(cude_ctx* ctx, int32_t* n_ranks, int32_t* rank, int32_t* 
  * "dense_chunk" (cude_simulate: output times per launch, 0 = ~1 GB of scratch; tests force several launches with it),
  * "dense_layout" (cude_simulate, suppression model: 0 = the caller's layout written directly, the default; 1 =
  * lane-contiguous rows + a transpose kernel), "refine_fused" (cude_refine_conditional in fixed-step mode: 1 = the one-launch
- * kernel, the default; 0 = one tangent launch per evaluation).  Values are decimal integers as text unless noted.  Every option is also read once
+ * kernel, the default; 0 = one tangent launch per evaluation), "profile_chunk" (cude_profile_conditional / cude_profile_intervals:
+ * grid points per launch, 0 = ~512 MB of scratch; tests force several launches with it).  Values are decimal integers as text unless noted.  Every option is also read once
  * at cude_create from its environment variable (CUDE_CPEP_PATH, CUDE_CPEP_KEEP, CUDE_SUPP_STORE, CUDE_SUPP_CKPT,
- * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED).
+ * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED, CUDE_PROFILE_CHUNK).
  * Options that shape the launch path take effect at the next cude_set_population_*.  No reference line: these are
  * properties of this implementation. */
 int32_t cude_set_option(cude_ctx* ctx, const char* name, const char* value);
