@@ -35,7 +35,7 @@ namespace cude {
 // ---------------------------------------------------------------------------------- dispatch
 template <class M, bool IS_CPEP>
 static hipError_t launch_adaptive(const typename M::Args& a, int extra_rows, bool grad, hipStream_t s) {
-    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const int64_t nblocks = grad ? (a.N + kBlock - 1) / kBlock : launch_blocks(a);
     const size_t lds = sizeof(double) * (size_t)(adaptive_rows<M>(grad) + extra_rows) * kBlock;
     const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
     if (grad && (a.tape == nullptr || a.tape_cap < 1 || a.g_cond == nullptr)) return hipErrorInvalidValue;
@@ -50,10 +50,11 @@ static hipError_t launch_adaptive(const typename M::Args& a, int extra_rows, boo
 // outputs-only launch of the suppression model (dense output, SuppArgs::T_data > 0; M = SuppAdOut): forward only
 template <class M>
 static hipError_t launch_adaptive_out(const SuppArgs& a, hipStream_t s) {
-    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const int64_t nblocks = launch_blocks(a);
     const size_t lds = sizeof(double) * (size_t)adaptive_rows<M>(false) * kBlock;
-    if (a.traj == nullptr || a.n_sets > 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((adaptive_kernel<M, false, false>), dim3((unsigned)nblocks), dim3(kBlock), lds, s, a);
+    const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
+    if (a.traj == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((adaptive_kernel<M, false, false>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     return hipGetLastError();
 }
 

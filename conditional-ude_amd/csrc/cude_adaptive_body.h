@@ -31,11 +31,13 @@ void adaptive_kernel(typename M::Args a) {
     double* s_Y = s_B + 7 * NS * kBlock;
     const int lane = threadIdx.x;
     if constexpr (M::NetT::USES_TANH) tanh_tab_init(lane);
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
+    const int64_t gid = ((int64_t)blockIdx.x + (GRAD ? 0 : a.blk_first)) * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t slot = active ? gid : a.N - 1;                       // position in the launch (lane order) ...
     const int64_t i = a.perm != nullptr ? (int64_t)a.perm[slot] : slot;  // ... and the subject that sits there
     const int64_t set = blockIdx.y;
+    // (dense output of several sets, forward launches only: set k's trajectories start traj_set_stride further on)
+    if constexpr (!GRAD) { if (a.traj != nullptr) a.traj += set * a.traj_set_stride; }
     cptr_t tout = as_const(a.out_times);
     const int n_out = a.T;
 #define KROW(j, s) s_K[((j) * NS + (s)) * kBlock + lane]

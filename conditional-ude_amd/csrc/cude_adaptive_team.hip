@@ -55,11 +55,13 @@ __global__ __launch_bounds__(kBlock*(kTeam + (GRAD ? 1 : 0))) void adaptive_team
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kBlock);
     double* const s_prod = smem + kRedRows * kBlock;
     double* const s_model = s_prod + 2 * kTeam * kBlock;
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
+    const int64_t gid = ((int64_t)blockIdx.x + (GRAD ? 0 : a.blk_first)) * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t slot = active ? gid : a.N - 1;                          // position in the launch (lane order) ...
     const int64_t i = a.perm != nullptr ? (int64_t)a.perm[slot] : slot;   // ... and the subject that sits there
     const int64_t set = blockIdx.y;
+    // (dense output of several sets, forward launches only: set k's trajectories start traj_set_stride further on)
+    if constexpr (!GRAD) { if (a.traj != nullptr) a.traj += set * a.traj_set_stride; }
     const bool lead = wave == 0;                   // the wave that writes what must be written once
     cptr_t tout = as_const(a.out_times);
     const int n_out = a.T;
@@ -402,7 +404,7 @@ __global__ __launch_bounds__(kBlock*(kTeam + (GRAD ? 1 : 0))) void adaptive_team
 
 template <class M>
 static hipError_t launch_team(const typename M::Args& a, bool grad, hipStream_t s) {
-    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const int64_t nblocks = grad ? (a.N + kBlock - 1) / kBlock : launch_blocks(a);
     const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
     const size_t lds = sizeof(double) * (size_t)(kRedRows + 2 * kTeam + 2 * a.TG + (grad ? M::NetT::NACC + 2 * 7 + 2 : 0) +
                                                  (grad && team_adjoints_in_lds<M, true>() ? 7 * M::NS : 0)) * kBlock;
@@ -424,7 +426,7 @@ static hipError_t launch_team(const typename M::Args& a, bool grad, hipStream_t 
 hipError_t launch_cpep_adaptive_team(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
     if (net.general() || net.generic() || net.symbolic() || a.team < 0) return hipErrorNotSupported;
     if (a.TG < 2 || a.TG > kUnrolledKnots || a.T < 1) return hipErrorNotSupported;
-    const int64_t waves1 = ((a.N + kBlock - 1) / kBlock) * (a.n_sets > 0 ? a.n_sets : 1);
+    const int64_t waves1 = (grad ? (a.N + kBlock - 1) / kBlock : launch_blocks(a)) * (a.n_sets > 0 ? a.n_sets : 1);
     if (waves1 > kTeamMaxWaves) return hipErrorNotSupported;
     if (grad && a.obs == nullptr) return hipErrorInvalidValue;
 #define X(NIN, W, D) \

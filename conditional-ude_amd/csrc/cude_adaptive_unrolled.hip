@@ -37,11 +37,13 @@ void adaptive_unrolled_kernel(typename M::Args a) {
     double* const s_B = smem + kRedRows * kBlock;
     const int lane = threadIdx.x;
     if constexpr (M::NetT::USES_TANH) tanh_tab_init(lane);
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
+    const int64_t gid = ((int64_t)blockIdx.x + (GRAD ? 0 : a.blk_first)) * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t slot = active ? gid : a.N - 1;
     const int64_t i = a.perm != nullptr ? (int64_t)a.perm[slot] : slot;
     const int64_t set = blockIdx.y;
+    // (dense output of several sets, forward launches only: set k's trajectories start traj_set_stride further on)
+    if constexpr (!GRAD) { if (a.traj != nullptr) a.traj += set * a.traj_set_stride; }
     cptr_t tout = as_const(a.out_times);
     const int n_out = a.T;
 
@@ -336,7 +338,7 @@ void adaptive_unrolled_kernel(typename M::Args a) {
 
 template <class M>
 static hipError_t launch_unrolled(const typename M::Args& a, bool grad, hipStream_t s) {
-    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const int64_t nblocks = grad ? (a.N + kBlock - 1) / kBlock : launch_blocks(a);
     const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
     const size_t lds = sizeof(double) * (size_t)((grad ? unrolled_fixed_rows<M, true>() : unrolled_fixed_rows<M, false>()) +
                                                   2 * a.TG) * kBlock;

@@ -27,11 +27,13 @@ void adaptive_unrolled_supp_kernel(SuppArgs a) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
     if constexpr (Net::USES_TANH) tanh_tab_init(lane);
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
+    const int64_t gid = ((int64_t)blockIdx.x + (GRAD ? 0 : a.blk_first)) * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t slot = active ? gid : a.N - 1;
     const int64_t i = a.perm != nullptr ? (int64_t)a.perm[slot] : slot;
     const int64_t set = blockIdx.y;
+    // (dense output of several sets, forward launches only: set k's trajectories start traj_set_stride further on)
+    if constexpr (!GRAD) { if (a.traj != nullptr) a.traj += set * a.traj_set_stride; }
     cptr_t tout = as_const(a.out_times);
     const int n_out = a.T;
 
@@ -356,10 +358,11 @@ static hipError_t launch_unrolled_supp(const SuppArgs& a, bool grad, hipStream_t
 // outputs-only launch (dense output, SuppArgs::T_data > 0; M = SuppAdOut): forward only
 template <class M>
 static hipError_t launch_unrolled_supp_out(const SuppArgs& a, hipStream_t s) {
-    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    const int64_t nblocks = launch_blocks(a);
     const size_t lds = sizeof(double) * (size_t)kRedRows * kBlock;
-    if (a.traj == nullptr || a.n_sets > 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((adaptive_unrolled_supp_kernel<M, false>), dim3((unsigned)nblocks), dim3(kBlock), lds, s, a);
+    const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
+    if (a.traj == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((adaptive_unrolled_supp_kernel<M, false>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     return hipGetLastError();
 }
 

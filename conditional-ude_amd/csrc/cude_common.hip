@@ -677,6 +677,30 @@ __global__ __launch_bounds__(64 * kProfileWaves) void profile_reduce_kernel(Prof
     a.p_imin[r] = p.imin; a.p_first[r] = p.first; a.p_last[r] = p.last; a.p_cnt[r] = p.cnt;
 }
 
+// cude_evaluate_conditional_sets: sets [k0, k0 + kn) of per-subject values x[k][i] and their SSEs into the running minimum
+// of F and its set index -- rule 3's minimum (strict <: the first minimum wins; a non-finite F never wins) with a value of
+// the subject's own per set.  One lane per subject walks the sets in order: a set's row is one coalesced read per wave.
+__global__ void best_of_sets_kernel(int64_t N, int k0, int kn, const double* __restrict__ sse, const double* __restrict__ x,
+                                    double pw, double pc, double* __restrict__ fmin, int32_t* __restrict__ imin) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    double f0 = k0 == 0 ? __builtin_huge_val() : fmin[i];
+    int32_t i0 = k0 == 0 ? 0 : imin[i];
+    for (int k = 0; k < kn; k++) {
+        const double f = profile_objective(sse[(int64_t)k * N + i], x[(int64_t)k * N + i], pw, pc);
+        if (f < f0) { f0 = f; i0 = k0 + k; }
+    }
+    fmin[i] = f0;
+    imin[i] = i0;
+}
+
+hipError_t launch_best_of_sets(int64_t N, int k0, int kn, const double* sse, const double* x, double pw, double pc, double* fmin,
+                               int32_t* imin, hipStream_t s) {
+    const int bs = 64;
+    hipLaunchKernelGGL(best_of_sets_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, s, N, k0, kn, sse, x, pw, pc, fmin, imin);
+    return hipGetLastError();
+}
+
 // the chunk's `ny` partial rows, in order, behind the running state of the chunks before it
 __global__ void profile_merge_kernel(ProfileArgs a, int ny) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -209,6 +209,8 @@ const OptionEntry kOptions[] = {
     {"dense_layout", "CUDE_DENSE_LAYOUT", &Options::dense_layout, false, false},
     {"refine_fused", "CUDE_REFINE_FUSED", &Options::refine_fused, false, false},
     {"profile_chunk", "CUDE_PROFILE_CHUNK", &Options::profile_chunk, false, false},
+    {"predictive_subjects", "CUDE_PREDICTIVE_SUBJECTS", &Options::predictive_subjects, false, false},
+    {"predictive_times", "CUDE_PREDICTIVE_TIMES", &Options::predictive_times, false, false},
 };
 }  // namespace
 

@@ -41,12 +41,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
     double* s_res = s_red + REDROWS * kBlock;   // [T][kBlock] residuals kept for the reverse sweep
 
     const int lane = threadIdx.x;
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
+    const int64_t gid = ((int64_t)blockIdx.x + (GRAD ? 0 : a.blk_first)) * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t i = active ? gid : a.N - 1;
     const int64_t N = a.N;
     // multi-start screening: blockIdx.y selects one of n_sets (network, conditional) parameter sets
     const int64_t set = blockIdx.y;
+    // (dense output of several sets, forward launches only: set k's trajectories start traj_set_stride further on)
+    if constexpr (!GRAD) { if (a.traj != nullptr) a.traj += set * a.traj_set_stride; }
     cptr_t p = as_const(a.nn + set * a.set_stride_nn);
     cptr_t phi = as_const(a.phi);
     cptr_t obs_w = as_const(a.obs_w);

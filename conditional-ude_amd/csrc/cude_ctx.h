@@ -91,6 +91,10 @@ struct Options {
                                 //   tangent launch + one update launch per evaluation (0: the form the adaptive mode always runs)
     int profile_chunk = 0;      // "profile_chunk" / CUDE_PROFILE_CHUNK: grid points per launch of cude_profile_conditional / cude_profile_intervals
                                 //   (0 = as many as ~512 MB of scratch allow; tests force several launches with it)
+    int predictive_subjects = 0; // "predictive_subjects" / CUDE_PREDICTIVE_SUBJECTS: subjects per solve launch of cude_predictive_bands,
+                                //   rounded up to whole workgroups of 64 (0 = as many as ~1 GB of sample trajectories allow)
+    int predictive_times = 0;   // "predictive_times" / CUDE_PREDICTIVE_TIMES: its output times per launch (0 = all of them unless 64
+                                //   subjects alone exceed that budget); tests force several launches in either dimension with them
     // ("hidden_activation" = tanh | relu | sigmoid, "output_activation" = softplus | identity: kept in cude_ctx::net)
     // ---- ablation
     int mixed = 1;              // CUDE_NO_MIXED

@@ -117,6 +117,9 @@ struct CpepArgs {
     const int32_t* perm;     // adaptive kernels: lane `gid` works on subject perm[gid] (nullptr = identity).  Lanes of a wave
                              // run as long as the slowest of them: cude_adaptive_regroup orders the subjects by their
                              // accepted-step counts so that a wave's lanes finish together.  The tape is kept in LANE order.
+    // dense output of several parameter sets (cude_predictive_bands): set k writes traj + k * traj_set_stride; forward
+    // launches start at workgroup blk_first of the population and cover blk_count of them (0 / 0 / 0: as ever)
+    int64_t traj_set_stride, blk_first;
 #ifdef CUDE_WAVE_TIMING
     long long* dbg;          // development builds only: [nblocks][4] = {start, end of forward, end, hw id} per wave
 #endif
@@ -258,7 +261,13 @@ struct SuppArgs {
     // residual, no SSE, no partials: the states go to traj[s * traj_ss + oi * traj_st + i * traj_sn] (subject i).
     int32_t T_data;
     int64_t traj_ss, traj_st, traj_sn;
+    // ... of several parameter sets (cude_predictive_bands): set k writes traj + k * traj_set_stride; the launch starts at
+    // workgroup blk_first of the population and covers blk_count of them (0 = the rest); 0 / 0 / 0: as ever
+    int64_t traj_set_stride, blk_first, blk_count;
 };
+// workgroups of a one-lane launch: the whole population, or the stretch the argument block names
+template <class A>
+inline int64_t launch_blocks(const A& a) { return a.blk_count > 0 ? a.blk_count : (a.N + kBlock - 1) / kBlock; }
 
 // Forward-mode (tangent-linear) solves, cude_sensitivity (cude_sens.hip): the population and solver fields of the model's
 // own argument block, and the three per-subject outputs of the tangent (any of them nullptr = not wanted).  Blocks of their
@@ -512,6 +521,25 @@ hipError_t launch_profile_finish(const ProfileArgs& a, const ProfileEnds& e, hip
 // one sectioning round with m interior points per end: resolve = 0 places the 2m candidates [2m][N], 1 moves the brackets
 hipError_t launch_profile_round(const ProfileArgs& a, const ProfileEnds& e, int m, int resolve, double* cand, const double* sse,
                                 hipStream_t s);
+// per-subject best of n_sets objectives (cude_evaluate_conditional_sets, cude_common.hip): sets [k0, k0 + kn) of sse / x
+// ([kn][N] each) into the running minimum fmin [N] and its set index imin [N]; F as cude_profile_intervals rule 1
+hipError_t launch_best_of_sets(int64_t N, int k0, int kn, const double* sse, const double* x, double pw, double pc, double* fmin,
+                               int32_t* imin, hipStream_t s);
+// exact order statistics and the sequential mean of every (subject, output time) column of a multi-set dense-output slab
+// (cude_predictive_bands, cude_predictive.hip).  slab: value of set k, column q at slab[k * set_stride + q * col_stride];
+// columns q in [0, n_cols) with q = j + Tc * (subject - first subject of the launch), j the time inside the chunk
+constexpr int kPredMaxSets = 4096, kPredMaxRanks = 16;
+struct PredictiveArgs {
+    const double* slab; int64_t set_stride, col_stride, n_cols;
+    int32_t K, Tc, n_ranks;
+    int64_t subj0; int32_t t0, n_times;          // position of the launch's first column in the outputs
+    double* order; double* mean;                 // [n_ranks x n_times x N], [n_times x N] or nullptr
+    uint8_t* bad; int64_t bad_stride;            // bad[subject * bad_stride + k] = 1: set k of the subject held a non-finite value
+};
+hipError_t launch_predictive_select(const PredictiveArgs& a, const int32_t* ranks_dev, hipStream_t s);
+size_t predictive_lds_bytes(int K, int* tile_cols);
+// bad_sets[i] = number of flagged sets of subject i
+hipError_t launch_predictive_count(int64_t N, int K, const uint8_t* bad, int32_t* bad_sets, hipStream_t s);
 hipError_t launch_fill(int64_t N, double v, double* out, hipStream_t s);
 hipError_t launch_fill_rows(int64_t N, int n_rows, const double* values, double* out, hipStream_t s);
 // population preparation

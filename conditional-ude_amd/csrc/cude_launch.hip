@@ -875,6 +875,35 @@ int64_t profile_chunk_sets(cude_ctx* c, int64_t n_points) {
     if (c->opt.profile_chunk > 0) chunk = std::min<int64_t>(chunk, c->opt.profile_chunk);
     return chunk;
 }
+
+// Dense output (cude_simulate, cude_predictive_bands): the output times must lie inside the population's time span and
+// not decrease
+int32_t check_output_times(const cude_ctx* c, int32_t n_times, const double* times) {
+    const double t0 = c->tp.front(), t1 = c->tp.back(), h = adaptive(c) ? (t1 - t0) : (t1 - t0) / c->cfg.n_steps;
+    for (int i = 0; i < n_times; i++) {
+        if (!(times[i] >= t0 - 1e-9 * h && times[i] <= t1 + 1e-9 * h))
+            return fail(CUDE_ERR_ARG, "output times must lie inside the time span of the population");
+        if (i > 0 && !(times[i] >= times[i - 1])) return fail(CUDE_ERR_ARG, "output times must be non-decreasing");
+    }
+    return CUDE_OK;
+}
+// ... and in fixed-step mode the step every output falls into (as locate_obs: tau in (t_n, t_{n+1}]), its seven
+// interpolation weights and, for the suppression model, state 1 at the outputs (the closed form of the launch tables)
+void output_tables(const cude_ctx* c, int64_t n, const double* times, std::vector<int32_t>& step, std::vector<double>& w,
+                   std::vector<double>& rho) {
+    const int S = c->cfg.n_steps;
+    const double t0 = c->tp.front(), h = (c->tp.back() - t0) / S;
+    step.resize((size_t)n);
+    w.resize((size_t)n * 7);
+    for (int64_t i = 0; i < n; i++) {
+        const double x = (times[i] - t0) / h;
+        int m = (int)std::ceil(x - 1e-9) - 1;
+        m = std::min(std::max(m, 0), S - 1);
+        step[(size_t)i] = m;
+        interp_weights((times[i] - (t0 + m * h)) / h, &w[(size_t)i * 7]);
+    }
+    if (!is_cpep(c)) supp_output_rho(S, h, step, w, rho);
+}
 }  // namespace
 
 extern "C" {
@@ -914,13 +943,8 @@ int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double*
     if (!c->have_nn || !c->have_cond) return fail(CUDE_ERR_STATE, "parameters not set");
     if (n_times < 1 || !times || !traj) return fail(CUDE_ERR_ARG, "null/empty input");
     const bool cpep = is_cpep(c);
-    const int S = c->cfg.n_steps, NS = cpep ? c->cfg.n_state : 3;
-    const double t0 = c->tp.front(), t1 = c->tp.back(), h = adaptive(c) ? (t1 - t0) : (t1 - t0) / S;
-    for (int i = 0; i < n_times; i++) {
-        if (!(times[i] >= t0 - 1e-9 * h && times[i] <= t1 + 1e-9 * h))
-            return fail(CUDE_ERR_ARG, "output times must lie inside the time span of the population");
-        if (i > 0 && !(times[i] >= times[i - 1])) return fail(CUDE_ERR_ARG, "output times must be non-decreasing");
-    }
+    const int NS = cpep ? c->cfg.n_state : 3;
+    if ((rc = check_output_times(c, n_times, times))) return rc;
     const int64_t N = c->N;
     // output times per launch: ~1 GB of trajectory scratch at most (every launch integrates from t_0 again)
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_times, (int64_t)(1e9 / (8.0 * NS * (double)N))));
@@ -950,21 +974,10 @@ int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double*
             // outputs a failed solve does not reach stay NaN
             HIP_TRY(hipMemsetAsync(dst, 0xff, (size_t)NS * kn * N * sizeof(double), c->stream));
         } else {
-            step.resize(kn);
-            w.resize((size_t)kn * 7);
-            for (int64_t i = 0; i < kn; i++) {              // as locate_obs: tau in (t_n, t_{n+1}]
-                const double x = (times[k0 + i] - t0) / h;
-                int n = (int)std::ceil(x - 1e-9) - 1;
-                n = std::min(std::max(n, 0), S - 1);
-                step[i] = n;
-                interp_weights((times[k0 + i] - (t0 + n * h)) / h, &w[(size_t)i * 7]);
-            }
+            output_tables(c, kn, times + k0, step, w, rho);
             HIP_TRY(hipMemcpyAsync(d_step.p, step.data(), kn * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync(d_w.p, w.data(), kn * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            if (!cpep) {                                    // state 1 at the outputs: the closed form of the launch tables
-                supp_output_rho(S, h, step, w, rho);
-                HIP_TRY(hipMemcpyAsync(d_rho.p, rho.data(), kn * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            }
+            if (!cpep) HIP_TRY(hipMemcpyAsync(d_rho.p, rho.data(), kn * sizeof(double), hipMemcpyHostToDevice, c->stream));
         }
         if (cpep) {
             cude::CpepArgs a = cpep_args(c);
@@ -994,6 +1007,177 @@ int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double*
                                  hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));           // step / w are reused by the next chunk
     }
+    return CUDE_OK;
+}
+
+int32_t cude_predictive_bands(cude_ctx* c, int32_t n_sets, const double* cond_sets, int32_t n_times, const double* times,
+                              int32_t state, int32_t n_ranks, const int32_t* ranks, double* order_out, double* mean_out,
+                              int32_t* bad_sets_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (c->net.generic())
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_predictive_bands: the network of this context runs on the fallback kernel "
+                                          "(cude_set_network), whose dense output takes one parameter set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_predictive_bands under stream capture");
+    if (n_sets < 1 || n_sets > cude::kPredMaxSets) return fail(CUDE_ERR_ARG, "need 1 <= n_sets <= 4096");
+    if (n_ranks < 0 || n_ranks > cude::kPredMaxRanks) return fail(CUDE_ERR_ARG, "need 0 <= n_ranks <= 16");
+    if (!cond_sets || n_times < 1 || !times) return fail(CUDE_ERR_ARG, "null/empty input");
+    if ((n_ranks > 0 && (!ranks || !order_out)) || (n_ranks == 0 && order_out) || (!order_out && !mean_out))
+        return fail(CUDE_ERR_ARG, "need order_out with n_ranks > 0 ranks, or mean_out, or both");
+    for (int32_t r = 0; r < n_ranks; r++)
+        if (ranks[r] < 0 || ranks[r] >= n_sets || (r > 0 && ranks[r] <= ranks[r - 1]))
+            return fail(CUDE_ERR_ARG, "ranks must be strictly increasing inside [0, n_sets)");
+    const bool cpep = is_cpep(c);
+    const int NS = cpep ? c->cfg.n_state : 3;
+    if (state < 0 || state >= NS) return fail(CUDE_ERR_ARG, "state out of range");
+    if ((rc = check_output_times(c, n_times, times))) return rc;
+    const int64_t N = c->N, K = n_sets, nb = c->nblocks;
+    const int P = c->P;
+    // The sample trajectories of one launch: [K][subjects][Tc][NS], ~1 GB at most.  Whole workgroups of subjects first (no
+    // solve is repeated); output times only when 64 subjects alone exceed the budget (each time chunk integrates from t_0)
+    const double budget = 1e9, per_time = 8.0 * NS * (double)K * cude::kBlock;     // bytes of one output time of one workgroup
+    int64_t Tc = n_times;
+    if (c->opt.predictive_times > 0) Tc = std::min<int64_t>(n_times, c->opt.predictive_times);
+    else if (per_time * n_times > budget) Tc = std::max<int64_t>(1, (int64_t)(budget / per_time));
+    int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)(budget / (per_time * (double)Tc))));
+    if (c->opt.predictive_subjects > 0)
+        blocks = std::min<int64_t>(nb, ((int64_t)c->opt.predictive_subjects + cude::kBlock - 1) / cude::kBlock);
+    const int64_t sub_max = std::min<int64_t>(N, blocks * cude::kBlock);
+    DevBuf<double> d_cond, d_slab, d_part, d_w, d_times, d_rho, d_order, d_mean;
+    DevBuf<int32_t> d_step, d_ranks, d_count;
+    DevBuf<uint8_t> d_bad;
+    HIP_TRY(d_cond.resize((size_t)K * N));
+    HIP_TRY(d_slab.resize((size_t)K * sub_max * Tc * NS));
+    if (cpep || adaptive(c)) HIP_TRY(d_part.resize((size_t)K * blocks * (P + 2)));
+    HIP_TRY(d_bad.resize((size_t)K * N));
+    HIP_TRY(d_count.resize((size_t)N));
+    if (n_ranks > 0) {
+        HIP_TRY(d_ranks.resize((size_t)n_ranks));
+        HIP_TRY(d_order.resize((size_t)n_ranks * n_times * N));
+        HIP_TRY(hipMemcpyAsync(d_ranks.p, ranks, n_ranks * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    if (mean_out) HIP_TRY(d_mean.resize((size_t)n_times * N));
+    HIP_TRY(hipMemcpyAsync(d_cond.p, cond_sets, (size_t)K * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_bad.p, 0, (size_t)K * N, c->stream));
+    // every output time's tables once (an entry depends on its own time alone): the chunks point into them
+    std::vector<int32_t> step;
+    std::vector<double> w, rho;
+    if (adaptive(c)) {
+        HIP_TRY(d_times.resize((size_t)n_times));
+        HIP_TRY(hipMemcpyAsync(d_times.p, times, n_times * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    } else {
+        output_tables(c, n_times, times, step, w, rho);
+        HIP_TRY(d_step.resize((size_t)n_times));
+        HIP_TRY(d_w.resize((size_t)n_times * 7));
+        HIP_TRY(hipMemcpyAsync(d_step.p, step.data(), n_times * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_w.p, w.data(), (size_t)n_times * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (!cpep) {
+            HIP_TRY(d_rho.resize((size_t)n_times));
+            HIP_TRY(hipMemcpyAsync(d_rho.p, rho.data(), n_times * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    for (int64_t b0 = 0; b0 < nb; b0 += blocks) {
+        const int64_t bn = std::min<int64_t>(blocks, nb - b0);
+        const int64_t s0 = b0 * cude::kBlock, sn = std::min<int64_t>(N, (b0 + bn) * cude::kBlock) - s0;
+        for (int64_t k0 = 0; k0 < n_times; k0 += Tc) {
+            const int64_t kn = std::min<int64_t>(Tc, n_times - k0);
+            const int64_t set_stride = (int64_t)NS * kn * sn;
+            // outputs a failed adaptive solve does not reach stay NaN
+            if (adaptive(c)) HIP_TRY(hipMemsetAsync(d_slab.p, 0xff, (size_t)K * set_stride * sizeof(double), c->stream));
+            // subject i of the population writes column block (i - s0) of the slab
+            double* const traj0 = d_slab.p - (int64_t)NS * kn * s0;
+            if (cpep) {
+                cude::CpepArgs a = cpep_args(c);
+                a.obs = nullptr;                            // no residuals: outputs only
+                a.perm = nullptr;                           // (a launch order would take subjects from outside the stretch)
+                a.cond = d_cond.p; a.nn = c->nn.p;
+                a.obs_step = d_step.p + k0; a.obs_w = d_w.p + 7 * k0; a.out_times = d_times.p + k0;
+                a.T = (int32_t)kn;
+                a.traj = traj0; a.partials = d_part.p;
+                a.n_sets = (int32_t)K; a.set_stride_nn = 0; a.set_stride_cond = N;
+                a.traj_set_stride = set_stride; a.blk_first = b0; a.blk_count = bn;
+                HIP_TRY(cude::launch_cpep(c->net, NS, false, a, c->stream));
+            } else {
+                cude::SuppArgs a = supp_args(c);
+                a.ckpt_steps_only = 0;
+                a.perm = nullptr;
+                a.cond = d_cond.p; a.nn = c->nn.p;
+                a.obs_step = d_step.p + k0; a.obs_w = d_w.p + 7 * k0; a.obs_rho = d_rho.p + k0; a.out_times = d_times.p + k0;
+                a.T = (int32_t)kn;
+                a.T_data = c->T;                            // outputs only: u0 = the data's first column
+                a.traj_ss = 1; a.traj_st = 3; a.traj_sn = 3 * kn;
+                a.traj = traj0; a.partials = d_part.p;
+                a.n_sets = (int32_t)K; a.set_stride_nn = 0; a.set_stride_cond = N;
+                a.traj_set_stride = set_stride; a.blk_first = b0; a.blk_count = bn;
+                HIP_TRY(cude::launch_supp(c->net, false, a, c->stream));
+            }
+            cude::PredictiveArgs pa{};
+            pa.slab = d_slab.p + state; pa.set_stride = set_stride; pa.col_stride = NS; pa.n_cols = kn * sn;
+            pa.K = (int32_t)K; pa.Tc = (int32_t)kn; pa.n_ranks = n_ranks;
+            pa.subj0 = s0; pa.t0 = (int32_t)k0; pa.n_times = n_times;
+            pa.order = d_order.p; pa.mean = d_mean.p;
+            pa.bad = d_bad.p; pa.bad_stride = K;
+            HIP_TRY(cude::launch_predictive_select(pa, d_ranks.p, c->stream));
+        }
+    }
+    if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }
+    HIP_TRY(cude::launch_predictive_count(N, (int)K, d_bad.p, d_count.p, c->stream));
+    std::vector<int32_t> count((size_t)N);
+    HIP_TRY(hipMemcpyAsync(count.data(), d_count.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (order_out)
+        HIP_TRY(hipMemcpyAsync(order_out, d_order.p, (size_t)n_ranks * n_times * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (mean_out)
+        HIP_TRY(hipMemcpyAsync(mean_out, d_mean.p, (size_t)n_times * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t failed = 0;
+    for (int64_t i = 0; i < N; i++) failed += count[(size_t)i] > 0;
+    c->last_failed = failed;
+    if (bad_sets_out) std::memcpy(bad_sets_out, count.data(), (size_t)N * sizeof(int32_t));
+    return CUDE_OK;
+}
+
+int32_t cude_evaluate_conditional_sets(cude_ctx* c, int32_t n_sets, const double* cond_sets, double penalty_weight,
+                                       double penalty_center, double* sse_out, int32_t* best_index_out,
+                                       double* best_objective_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_evaluate_conditional_sets under stream capture");
+    if (n_sets < 1 || !cond_sets) return fail(CUDE_ERR_ARG, "null/empty input");
+    if (!sse_out && !best_index_out && !best_objective_out) return fail(CUDE_ERR_ARG, "no output requested");
+    if (!(penalty_weight >= 0) || !std::isfinite(penalty_weight) || !std::isfinite(penalty_center))
+        return fail(CUDE_ERR_ARG, "need a finite penalty_weight >= 0 and a finite penalty_center");
+    const int64_t N = c->N;
+    const int64_t chunk = profile_chunk_sets(c, n_sets);
+    DevBuf<double> d_cond, d_sse, d_part, d_fmin;
+    DevBuf<int32_t> d_imin;
+    HIP_TRY(d_cond.resize((size_t)chunk * N));
+    HIP_TRY(d_sse.resize((size_t)chunk * N));
+    HIP_TRY(d_fmin.resize((size_t)N));
+    HIP_TRY(d_imin.resize((size_t)N));
+    if ((rc = reserve_sets_forward(c, chunk, false, d_part))) return rc;
+    SetsForward fwd;                                      // one network, kn sets of per-subject values
+    fwd.cond = d_cond.p; fwd.nn = c->nn.p; fwd.sse = d_sse.p; fwd.partials = d_part.p;
+    for (int64_t k0 = 0; k0 < n_sets; k0 += chunk) {
+        const int64_t kn = std::min<int64_t>(chunk, n_sets - k0);
+        HIP_TRY(hipMemcpyAsync(d_cond.p, cond_sets + k0 * N, kn * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        fwd.n_sets = (int)kn;
+        if ((rc = forward_sets(c, fwd))) return rc;
+        HIP_TRY(cude::launch_best_of_sets(N, (int)k0, (int)kn, d_sse.p, d_cond.p, penalty_weight, penalty_center, d_fmin.p,
+                                          d_imin.p, c->stream));
+        if (sse_out)
+            HIP_TRY(hipMemcpyAsync(sse_out + k0 * N, d_sse.p, kn * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        // (d_cond / d_sse are the next chunk's too; copies from and to pageable memory are staged by the runtime in
+        //  stream order, so only the last chunk needs the host to wait)
+    }
+    if (best_index_out)
+        HIP_TRY(hipMemcpyAsync(best_index_out, d_imin.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (best_objective_out)
+        HIP_TRY(hipMemcpyAsync(best_objective_out, d_fmin.p, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return CUDE_OK;
 }
 

@@ -27,11 +27,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) voi
     extern __shared__ double smem[];
     double* s_K = smem;                  // [7][2] stage derivatives of states 2 and 3 (state 1 is a table lookup)
     const int lane = threadIdx.x;
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + lane;
+    const int64_t gid = ((int64_t)blockIdx.x + a.blk_first) * kBlock + lane;
     const bool active = gid < a.N;
     const int64_t i = active ? gid : a.N - 1;
     const int64_t N = a.N;
-    cptr_t p = as_const(a.nn);
+    const int64_t set = blockIdx.y;      // several parameter sets (cude_predictive_bands): one per grid row
+    cptr_t p = as_const(a.nn + set * a.set_stride_nn);
     cptr_t obs_w = as_const(a.obs_w);
     cptr_t rho = as_const(a.rho);
     cptr_t obs_rho = as_const(a.obs_rho);
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) voi
     const double h = a.h;
 #define KROW(j, s) s_K[((j) * 2 + (s)) * kBlock + lane]
 
-    double cst[1] = {exp(a.cond[i])};
+    double cst[1] = {exp(a.cond[set * a.set_stride_cond + i])};
     double c[W];
     Net::first_layer_offset(p, cst, c);
 #pragma unroll
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) voi
     // evaluation e = 0 is k_1 of step 0; e = 6n+st (st = 1..6) is stage st+1 of step n (st = 6: k_7 = f(y_{n+1}))
     int oi = 0, n = 0, st = 0;
     if constexpr (Net::USES_TANH) tanh_tab_init(lane, !Net::LDS_BIAS);
-    Net::bias_init(a.nn, lane);
+    Net::bias_init(a.nn + set * a.set_stride_nn, lane);
 #pragma unroll 1
     for (int e = 0; e <= 6 * S; e++) {
         double u[3];
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) voi
                 for (int s = 0; s < 2; s++) o[s] = fma(w, KROW(j, s), o[s]);
             }
             if (active) {
-                double* tr = a.traj + oi * a.traj_st + i * a.traj_sn;
+                double* tr = a.traj + set * a.traj_set_stride + oi * a.traj_st + i * a.traj_sn;
                 tr[0] = bad ? __builtin_nan("") : u10 * obs_rho[oi];
 #pragma unroll
                 for (int s = 0; s < 2; s++) tr[(s + 1) * a.traj_ss] = bad ? __builtin_nan("") : fma(h, o[s], y[s]);
@@ -121,9 +122,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) voi
 
 template <int W, int D, int HA = kActHiddenTanh, int OA = kActOutSoftplus>
 static hipError_t launch_dense(const SuppArgs& a, hipStream_t s) {
-    const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
-    if (a.rho == nullptr || a.obs_rho == nullptr || a.traj == nullptr || a.n_sets > 1 || a.S < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((supp_dense_kernel<W, D, HA, OA>), dim3((unsigned)nblocks), dim3(kBlock),
+    const int64_t nblocks = launch_blocks(a);
+    const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
+    if (a.rho == nullptr || a.obs_rho == nullptr || a.traj == nullptr || a.S < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((supp_dense_kernel<W, D, HA, OA>), dim3((unsigned)nblocks, n_sets), dim3(kBlock),
                        sizeof(double) * (size_t)(7 * 2) * kBlock, s, a);
     return hipGetLastError();
 }

@@ -75,6 +75,10 @@ _SIGNATURES = {
     "cude_profile_intervals": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_double,
                                            C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cude_predictive_bands": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cude_evaluate_conditional_sets": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]),
     "cude_mh_chain": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "cude_n_failed": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),

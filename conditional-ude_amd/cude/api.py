@@ -1118,6 +1118,25 @@ def simul(p, prob, individual_data, timepoints, *, n_steps=None):
     return pop.engine.simulate(tp)
 
 
+def suppression_predictive(p, theta_samples, prob, individual_data, timepoints, *, levels=(0.025, 0.5, 0.975), state=2,
+                           n_steps=None):
+    """`simul` for K sampled conditional vectors theta_samples (K, N) at once, summarised on the device
+    (cude_predictive_bands): the quantiles at `levels`, the mean, the minimum and the maximum of state `state` (0-based; 1
+    and 2 depend on theta) of every (individual, save time) column over the samples -- the suppression counterpart of
+    posterior_predictive.  Save times as `simul`'s dense-output form: inside prob.tspan, non-decreasing."""
+    data = np.asarray(individual_data, dtype=np.float64)
+    tp = np.asarray(timepoints, dtype=np.float64).reshape(-1)
+    if data.ndim != 3 or data.shape[0] != 3:
+        raise ValueError("individual_data must be (3, T, N)")
+    t0, t1 = getattr(prob, "tspan", (0.0, 30.0))
+    if tp.size == 0 or not (np.all(tp >= t0) and np.all(tp <= t1)) or np.any(np.diff(tp) < 0.0):
+        raise ValueError(f"suppression_predictive: save times must be non-decreasing inside ({t0}, {t1})")
+    u0 = np.ascontiguousarray(data[:, :1, :])
+    pop = _supp_population(prob, np.concatenate([u0, u0], axis=1), np.array([t0, t1]), 0.0, n_steps)
+    pop.engine.set_params(p.neural, None)
+    return _predictive(pop.engine, theta_samples, tp, levels, state)
+
+
 def fit_suppression_model(p_init, prob, data, timepoints, lam, *, select_best_n=1, adam_iters=2000, lbfgs_iters=2000,
                           n_steps=None, side_by_side=True):
     """fit_suppression_model (:132-177): screen all initials, keep the best n, Adam() [eta = 1e-3] then L-BFGS.
@@ -1334,13 +1353,76 @@ def SAEM(models, timepoints, cpeptide_data, initial_neural_params, *, sigma=1.0,
                      device_seed=device_seed, subject_offset=subject_offset)
 
 
+def quantile_ranks(levels, K):
+    """The order statistics the type-7 quantiles (Julia's `quantile`, numpy.quantile's default) of K values need: with
+    h = (K - 1) q the quantile at level q is x[lo] + g (x[hi] - x[lo]), lo = floor(h), hi = min(lo + 1, K - 1), g = h - lo.
+    Returns (ranks, lo, hi, g): ranks = the sorted unique lo / hi of all levels (what cude_predictive_bands is asked for),
+    lo / hi = every level's positions IN `ranks`, g = its weight."""
+    q = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if K < 1 or np.any(~((q >= 0.0) & (q <= 1.0))):
+        raise ValueError("quantile_ranks: need K >= 1 and levels inside [0, 1]")
+    h = (K - 1) * q
+    lo = np.floor(h).astype(np.int64)
+    hi = np.minimum(lo + 1, K - 1)
+    ranks = np.unique(np.concatenate([lo, hi]))
+    return ranks.astype(np.int32), np.searchsorted(ranks, lo), np.searchsorted(ranks, hi), h - lo
+
+
+def quantile_lerp(x_lo, x_hi, g):
+    """The type-7 value x_lo + g (x_hi - x_lo), anchored at the nearer neighbour: evaluated as x_hi - (1 - g) (x_hi - x_lo)
+    for g >= 1/2.  The same number; the roundings of the product and of the last operation are then relative to the
+    neighbour the result lies next to, not to the far one.  numpy.quantile evaluates its default rule this way too."""
+    d = x_hi - x_lo
+    return np.where(g >= 0.5, x_hi - d * (1 - g), x_lo + d * g)
+
+
+def _predictive(eng, samples, times, levels, state):
+    """quantiles (N, n_levels, n_times), mean, minimum and maximum (N, n_times) of the sample curves, from the order
+    statistics and the mean cude_predictive_bands leaves (the envelope ranks 0 and K - 1 ride along)."""
+    s = np.asarray(samples, dtype=np.float64)
+    K = s.shape[0]
+    ranks, lo, hi, g = quantile_ranks(levels, K)
+    all_ranks = np.unique(np.concatenate([ranks, [0, K - 1]])).astype(np.int32)
+    r = eng.predictive_bands(s, times, all_ranks, state=state)
+    order = r["order"]                                     # (N, n_times, n_ranks)
+    pos = np.searchsorted(all_ranks, ranks)
+    x_lo, x_hi = order[:, :, pos[lo]], order[:, :, pos[hi]]
+    quant = quantile_lerp(x_lo, x_hi, g).transpose(0, 2, 1)
+    return SimpleNamespace(quantiles=np.ascontiguousarray(quant), mean=r["mean"], minimum=order[:, :, 0].copy(),
+                           maximum=order[:, :, -1].copy(), levels=np.asarray(levels, dtype=np.float64),
+                           times=np.asarray(times, dtype=np.float64), bad_sets=r["bad_sets"])
+
+
+def posterior_predictive(p_neural, samples, models, timepoints, cpeptide_data, *, out_timepoints=None,
+                         levels=(0.025, 0.5, 0.975), save_idxs=1, n_steps=None):
+    """The posterior-predictive curves of c-peptide/06-saem.jl:209-223 for ALL individuals at once, summarised on the
+    device: samples (K, N) -- e.g. the thinned chain `individual_effects(...).samples[999::10]` -- are simulated as
+    `simulate` does (state `save_idxs`, 1-based, at `out_timepoints`) and reduced there to the quantiles at `levels` (the
+    type-7 rule of Julia's `quantile`), the mean, the minimum and the maximum of every (individual, time) column.
+    Returns a namespace: quantiles (N, n_levels, n_times); mean, minimum, maximum (N, n_times); bad_sets (N,) = samples
+    whose solve gave a non-finite value (such a column is NaN throughout)."""
+    sym = isinstance(models[0], CPeptideODEModel)
+    pop = _population(models, timepoints, cpeptide_data, n_steps, cond_space="raw" if sym else "log")
+    pop.engine.set_params(pop.shared if sym else p_neural, None)
+    times = np.asarray(timepoints if out_timepoints is None else out_timepoints, dtype=np.float64)
+    return _predictive(pop.engine, samples, times, levels, save_idxs - 1)
+
+
 def individual_effects(models, timepoints, cpeptide_data, saem_result, *, n_samples=3000, proposal_std=0.3,
-                       rng=None, n_steps=None, lower=-6.0, upper=4.0):
+                       rng=None, n_steps=None, lower=-6.0, upper=4.0, predictive_times=None, starts="search",
+                       burn_in=None, thin=10, levels=(0.025, 0.5, 0.975)):
     """The per-individual loop that follows SAEM in c-peptide/06-saem.jl:97-135, for ALL individuals at once:
     posterior samples of the conditional parameter (n_samples Metropolis steps from the population mean, every
     state kept, :107-112), the MAP mode (minimiser of -(log-likelihood + log prior), :114-119), the MLE estimate
     (:121-126) and `mse = -2 individual_log_likelihood(mode; sigma = 1)` = the SSE at the mode (:129).  The two 1-D
-    optimisations are bracketing searches over [lower, upper] with one forward launch per probe."""
+    optimisations are bracketing searches over [lower, upper] with one forward launch per probe.
+    starts = "samples": they are cude_refine_conditional runs from each individual's best kept sample instead -- the
+    `argmin(map_objective_values)` / `argmax(likelihood_values)` over `samples[1000:end]` the reference starts its LBFGS
+    runs from (:226-236), found on the device (cude_evaluate_conditional_sets).  predictive_times: the result also holds
+    `predictive`, the bands of the thinned kept chain `samples[1000:10:end]` at those times (posterior_predictive, :220).
+    Kept samples: from `burn_in` on (default 999, a third of the chain when it is shorter than 1000 steps)."""
+    if starts not in ("search", "samples"):
+        raise ValueError("starts must be 'search' or 'samples'")
     rng = np.random.default_rng() if rng is None else rng
     pop = _population(models, timepoints, cpeptide_data, n_steps)
     eng, N, T = pop.engine, pop.N, pop.T
@@ -1348,12 +1430,26 @@ def individual_effects(models, timepoints, cpeptide_data, saem_result, *, n_samp
     eng.set_params(saem_result.p_neural, np.full(N, prior))
     acc, samples = eng.mh_chain(rng.standard_normal((n_samples, N)), rng.random((n_samples, N)), sigma, prior, omega,
                                 proposal_std)
+    burn = (999 if n_samples > 1000 else n_samples // 3) if burn_in is None else int(burn_in)
+    kept = samples[burn:]
 
     # -(log-likelihood + log prior) = [SSE + (sigma/Omega)^2 (b - prior)^2] / (2 sigma^2) + const
-    modes, _, mse = eng.fit_conditional(lower, upper, 81, 48, (sigma / omega) ** 2, prior)
-    mle, _, _ = eng.fit_conditional(lower, upper, 81, 48)
-    return SimpleNamespace(samples=samples, modes=modes, mle=mle, mse=mse,
-                           acceptance_rate=float(acc.sum()) / (n_samples * N))
+    if starts == "search":
+        modes, _, mse = eng.fit_conditional(lower, upper, 81, 48, (sigma / omega) ** 2, prior)
+        mle, _, _ = eng.fit_conditional(lower, upper, 81, 48)
+    else:
+        cols = np.arange(N)
+        lo, hi = min(lower, float(kept.min())), max(upper, float(kept.max()))
+        best = eng.evaluate_conditional_sets(kept, (sigma / omega) ** 2, prior)["index"]
+        r = eng.refine_conditional(kept[best, cols], lo, hi, penalty_weight=(sigma / omega) ** 2, penalty_center=prior)
+        modes, mse = r["x"], r["sse"]
+        best = eng.evaluate_conditional_sets(kept)["index"]
+        mle = eng.refine_conditional(kept[best, cols], lo, hi)["x"]
+    out = SimpleNamespace(samples=samples, modes=modes, mle=mle, mse=mse,
+                          acceptance_rate=float(acc.sum()) / (n_samples * N))
+    if predictive_times is not None:
+        out.predictive = _predictive(eng, kept[::thin], np.asarray(predictive_times, dtype=np.float64), levels, 0)
+    return out
 
 
 # ----------------------------------------------------------------------------- symbolic (Michaelis-Menten) model

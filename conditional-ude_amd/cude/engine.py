@@ -398,6 +398,39 @@ class Engine:
             _ptr(out["min"]), _ptr(out.get("center_objective")), _ptr(out.get("n_inside")), _ptr(out.get("status"))))
         return out
 
+    def predictive_bands(self, cond_sets, times, ranks, state=0, want_mean=True):
+        """Posterior-predictive bands on the device (cude_predictive_bands): cond_sets (K, N) -- the rows of mh_chain's
+        samples -- are solved as simulate(times) solves the context's own conditional parameters, and every (subject,
+        time) column of state `state` is reduced there to its order statistics `ranks` (strictly increasing, 0-based) and
+        its mean over the sets in set order.  Returns dict(order (N, n_times, n_ranks) -- None without ranks --, mean
+        (N, n_times) -- None unless want_mean --, bad_sets (N,) int32: sets with a non-finite value).  A column with a
+        non-finite value is NaN throughout; n_failed() afterwards counts the subjects with bad_sets > 0."""
+        cd = _f64(cond_sets)
+        if cd.ndim != 2 or cd.shape[1] != self.N:
+            raise ValueError(f"expected cond_sets (K, {self.N})")
+        t = _f64(times).reshape(-1)
+        rk = np.ascontiguousarray(np.asarray(ranks, dtype=np.int32).reshape(-1))
+        order = np.empty((self.N, t.size, rk.size)) if rk.size else None
+        mean = np.empty((self.N, t.size)) if want_mean else None
+        bad = np.empty(self.N, dtype=np.int32)
+        check(self._lib.cude_predictive_bands(self._h, cd.shape[0], _ptr(cd), t.size, _ptr(t), int(state), rk.size,
+                                              _ptr(rk) if rk.size else None, _ptr(order), _ptr(mean), _ptr(bad)))
+        return {"order": order, "mean": mean, "bad_sets": bad}
+
+    def evaluate_conditional_sets(self, cond_sets, penalty_weight=0.0, penalty_center=0.0, want_sse=False):
+        """SSE_i(cond_sets[k, i]) + penalty_weight (cond_sets[k, i] - penalty_center)^2 for every set and subject
+        (cude_evaluate_conditional_sets; cond_sets (K, N)), reduced on the device to the per-subject minimum: dict(index (N,)
+        int32 = the first set that attains it, objective (N,) -- +Inf and index 0 with no finite value --, sse (K, N) -- None
+        unless want_sse)."""
+        cd = _f64(cond_sets)
+        if cd.ndim != 2 or cd.shape[1] != self.N:
+            raise ValueError(f"expected cond_sets (K, {self.N})")
+        sse = np.empty(cd.shape) if want_sse else None
+        idx, obj = np.empty(self.N, dtype=np.int32), np.empty(self.N)
+        check(self._lib.cude_evaluate_conditional_sets(self._h, cd.shape[0], _ptr(cd), float(penalty_weight),
+                                                       float(penalty_center), _ptr(sse), _ptr(idx), _ptr(obj)))
+        return {"index": idx, "objective": obj, "sse": sse}
+
     def fit_conditional(self, lower, upper, n_grid=41, n_iters=48, penalty_weight=0.0, penalty_center=0.0):
         """All subjects' 1-D fits of the conditional parameter with the shared parameters frozen, on the device:
         argmin_x SSE_i(x) + penalty_weight (x - penalty_center)^2 over [lower, upper] -> (x[N], objective[N], sse[N])."""

@@ -272,6 +272,38 @@ function profile_intervals(c::Ctx, values::Vector{Float64}, center, delta; delta
     lower, upper, amin, fmin, fcen, n_inside, status
 end
 
+# posterior-predictive bands on the device (cude_predictive_bands): cond_sets N×K (column k = sample set k, the layout of
+# mh_chain's samples), solved as simulate(c, times) solves the context's own conditional parameters; every (subject, time)
+# column of state `state` (1-based) reduced there to its order statistics `ranks` (0-based, strictly increasing) and its
+# mean in set order.  Returns (order n_ranks×n_times×N, mean n_times×N, bad_sets N)
+function predictive_bands(c::Ctx, cond_sets::Matrix{Float64}, times::Vector{Float64}, ranks::Vector{Int32}; state = 1,
+                          want_mean = true)
+    size(cond_sets, 1) == c.N || error("cond_sets must be N×K")
+    K = size(cond_sets, 2); nr = length(ranks); nt = length(times)
+    order = Array{Float64}(undef, nr, nt, c.N)
+    mean = Matrix{Float64}(undef, nt, c.N)
+    bad = Vector{Int32}(undef, c.N)
+    GC.@preserve cond_sets times ranks order mean bad check(ccall((:cude_predictive_bands, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        c.h, K, cond_sets, nt, times, state - 1, nr, nr > 0 ? pointer(ranks) : C_NULL, nr > 0 ? pointer(order) : C_NULL,
+        want_mean ? pointer(mean) : C_NULL, bad))
+    order, (want_mean ? mean : nothing), bad
+end
+
+# SSEᵢ(cond_sets[i, k]) + penalty_weight (cond_sets[i, k] - penalty_center)² for every set, reduced on the device to the
+# per-subject minimum and the first set that attains it (cude_evaluate_conditional_sets): `likelihood_values` /
+# `map_objective_values` and their argmax / argmin (c-peptide/06-saem.jl:226-235).  Returns (index 1-based, objective, sse N×K)
+function evaluate_conditional_sets(c::Ctx, cond_sets::Matrix{Float64}; penalty_weight = 0.0, penalty_center = 0.0)
+    size(cond_sets, 1) == c.N || error("cond_sets must be N×K")
+    K = size(cond_sets, 2)
+    sse = Matrix{Float64}(undef, c.N, K)
+    idx = Vector{Int32}(undef, c.N); obj = Vector{Float64}(undef, c.N)
+    GC.@preserve cond_sets sse idx obj check(ccall((:cude_evaluate_conditional_sets, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+        c.h, K, cond_sets, penalty_weight, penalty_center, sse, idx, obj))
+    idx .+ Int32(1), obj, sse
+end
+
 adam_init!(c::Ctx, η; β1 = 0.9, β2 = 0.999, ϵ = 1e-8) =
     check(ccall((:cude_adam_init, LIB), Int32, (Ptr{Cvoid}, Float64, Float64, Float64, Float64), c.h, η, β1, β2, ϵ))
 

@@ -378,6 +378,54 @@ int32_t cude_profile_intervals(cude_ctx* ctx, int32_t n_points, const double* va
                                double* lower_out, double* upper_out, double* argmin_out, double* min_out,
                                double* center_objective_out, int32_t* n_inside_out, int32_t* status_out);
 
+/* Posterior-predictive bands from per-subject sample sets, reduced on the device -- the loop that simulates every thinned
+ * posterior sample (`test_samples[i][1000:10:end]`, ~200 per individual) on `t0:0.1:tend` and takes quantiles of the
+ * curves (c-peptide/06-saem.jl:209-241; the solve is `solve(prob, saveat = ...)` of src/saem.jl:31-53).  The host receives a
+ * few curves per subject, never the n_sets x n_times x N sample trajectories.
+ *   1. Solve: set k = the context's shared parameters with the conditional vector cond_sets[k] ([n_sets][N] row-major,
+ *      the row layout of cude_mh_chain's `samples`), solved exactly as cude_simulate solves the context's own conditional
+ *      parameters at `times` (the same kernels, arithmetic and time validation; adaptive mode: the accepted steps of
+ *      cude_forward at that vector).  v[k] at (subject i, time j) has the same bits as cude_simulate's state `state` after
+ *      cude_set_params(ctx, NULL, cond_sets[k]).
+ *   2. Order statistics: order_out[r + n_ranks (j + n_times i)] = the ranks[r]-th smallest (0-based) of v[0 .. n_sets-1] of
+ *      column (i, j); ranks strictly increasing, 0 <= ranks[r] < n_sets.  A selection: the result is one of the solve's own
+ *      values, bit for bit (rank 0 and rank n_sets - 1: the envelope).  1 <= n_sets <= 4096, 0 <= n_ranks <= 16; order_out
+ *      and mean_out may each be NULL, not both.
+ *   3. Mean: mean_out[j + n_times i] = (((v[0] + v[1]) + v[2]) + ...) / n_sets -- plain adds in set order, no fma, so the
+ *      value does not depend on how the work is split.
+ *   4. Non-finite values: a column that holds any non-finite value gets NaN in every order_out entry and in its mean (what
+ *      numpy.quantile returns; decided by a test on the values, not by how NaN sorts).  bad_sets_out[i] (optional) = the
+ *      number of sets with a non-finite value at any output time of subject i; cude_n_failed afterwards counts the
+ *      subjects with bad_sets > 0.  Other subjects are unaffected, bit for bit.  (The values decide: the c-peptide kernels
+ *      take the conditional parameter through exp and a table-based tanh, which map a NaN to finite numbers -- there a
+ *      NaN sample gives cude_simulate's finite trajectory and marks nothing; the suppression solves carry it through.)
+ *   5. Both network models, the symbolic model in either cond_space, fixed-step and adaptive mode, every tuned shape;
+ *      state < n_state (suppression state 0 does not depend on the parameter and is allowed).  CUDE_ERR_UNSUPPORTED for a
+ *      network on the fallback kernel (cude_set_network), CUDE_ERR_STATE under stream capture, CUDE_ERR_ARG for n_sets,
+ *      n_ranks, ranks, state or times out of range.  A sharded population needs no exchange.  Leaves the context's
+ *      parameters untouched.  Adaptive mode: cude_adaptive_steps refuses afterwards.
+ * The solves are split over subjects first (whole workgroups of 64: no solve is repeated) and over output times only when
+ * 64 subjects x n_sets x n_times exceed ~1 GB (every time chunk integrates from t_0 again, as cude_simulate's); options
+ * "predictive_subjects" / "predictive_times" force either split, and the result depends on neither.  Everything is queued
+ * on the context's stream; one synchronisation at the end. */
+int32_t cude_predictive_bands(cude_ctx* ctx, int32_t n_sets, const double* cond_sets, int32_t n_times, const double* times,
+                              int32_t state, int32_t n_ranks, const int32_t* ranks, double* order_out, double* mean_out,
+                              int32_t* bad_sets_out);
+
+/* The per-set objective of per-subject values and its per-subject argmin -- `likelihood_values` / `map_objective_values`
+ * over the kept samples and their `argmax` / `argmin`, from which the MLE / MAP LBFGS runs start
+ * (c-peptide/06-saem.jl:226-235).  SSE_i(cond_sets[k][i]) for every set ([n_sets][N] row-major) through
+ * cude_profile_conditional's launches, chunked like a profile scan (option "profile_chunk"): the SSE bits equal
+ * cude_profile_conditional's wherever a set holds one value for everybody.  F = SSE + pw (x - pc)^2 rounded as
+ * cude_profile_intervals rule 1; reduced on the device to best_objective_out[i] = min_k F and best_index_out[i] = its set
+ * index (strict <: the first minimum wins; a non-finite F is above everything; no finite value: index 0, +Inf).
+ * sse_out [n_sets][N], best_index_out [N], best_objective_out [N]: all optional, at least one.  Every model and both
+ * modes, the fallback kernel included; CUDE_ERR_STATE under stream capture.  Leaves the context's parameters untouched;
+ * adaptive mode: cude_adaptive_steps refuses afterwards. */
+int32_t cude_evaluate_conditional_sets(cude_ctx* ctx, int32_t n_sets, const double* cond_sets, double penalty_weight,
+                                       double penalty_center, double* sse_out, int32_t* best_index_out,
+                                       double* best_objective_out);
+
 /* SAEM E-step on the device: n_mc Metropolis-Hastings steps of every subject's conditional parameter
  * (`mcmc_step` src/saem.jl:86-108, applied n_mcmc_steps times with the stochastic-approximation update of the
  * chain state :177-186).  The chain state is the context's conditional parameters (updated in place); the
@@ -556,9 +604,12 @@ int32_t cude_xchg_info(cude_ctx* ctx, int32_t* n_ranks, int32_t* rank, int32_t* 
  * "dense_layout" (cude_simulate, suppression model: 0 = the caller's layout written directly, the default; 1 =
  * lane-contiguous rows + a transpose kernel), "refine_fused" (cude_refine_conditional in fixed-step mode: 1 = the one-launch
  * kernel, the default; 0 = one tangent launch per evaluation), "profile_chunk" (cude_profile_conditional / cude_profile_intervals:
- * grid points per launch, 0 = ~512 MB of scratch; tests force several launches with it).  Values are decimal integers as text unless noted.  Every option is also read once
+ * grid points per launch, 0 = ~512 MB of scratch; tests force several launches with it), "predictive_subjects" /
+ * "predictive_times" (cude_predictive_bands: subjects per solve launch, rounded up to 64, and output times per launch; 0 =
+ * by the ~1 GB budget of sample trajectories; tests force several launches in either dimension with them).  Values are decimal integers as text unless noted.  Every option is also read once
  * at cude_create from its environment variable (CUDE_CPEP_PATH, CUDE_CPEP_KEEP, CUDE_SUPP_STORE, CUDE_SUPP_CKPT,
- * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED, CUDE_PROFILE_CHUNK).
+ * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED, CUDE_PROFILE_CHUNK,
+ * CUDE_PREDICTIVE_SUBJECTS, CUDE_PREDICTIVE_TIMES).
  * Options that shape the launch path take effect at the next cude_set_population_*.  No reference line: these are
  * properties of this implementation. */
 int32_t cude_set_option(cude_ctx* ctx, const char* name, const char* value);
