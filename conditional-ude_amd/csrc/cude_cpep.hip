@@ -396,9 +396,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
                         for (int j = 0; j < Net::NCST; j++) f[j] = s_tab[(sr * Net::NCST + j) * kBlock + lane];
 #pragma unroll
                         for (int j = 0; j < Net::NCST; j++) asm volatile("" : "+v"(f[j]));
+                        // s is wave-uniform: a branch, not a select per lane (written as a select, the compiler
+                        // multiplies always and picks with two v_cndmask_b32 per unit; the pin on the copies keeps it
+                        // from converting the branch back)
+                        if (s < 4) {
 #pragma unroll
-                        for (int j = 0; j < Net::NCST; j++)
-                            E1.v[j] = s < 4 ? A.v[j] * f[j] : A.v[j];   // stage 5 sits at the anchor time itself
+                            for (int j = 0; j < Net::NCST; j++) E1.v[j] = A.v[j] * f[j];
+                        } else {                 // stage 5 sits at the anchor time itself
+#pragma unroll
+                            for (int j = 0; j < Net::NCST; j++) {
+                                E1.v[j] = A.v[j];
+                                asm volatile("" : "+v"(E1.v[j]));
+                            }
+                        }
                     }
                 }
                 s = (s == 0) ? 4 : s - 1;
@@ -431,6 +441,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
             }
         }
 
+        // Behind the sweep the whole dynamic allocation is dead (stage weights, factor table, residuals): where its
+        // fixed part alone -- (5 + REDROWS) rows, whatever T (launch_one) -- holds the doubled rows, the reduction
+        // reads them at constant offsets (block_reduce_expand_wide).  The other shapes allocate kRedRows rows only.
+        constexpr bool kWide = 5 + REDROWS >= kRedWideRows;
         if constexpr (kRW) {
             // the subject index and exp(beta) are formed again here: carried through the sweep, their four registers
             // are the ones the resident layer needs
@@ -441,10 +455,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
             double ce[NC];
             ce[0] = Net::cond_input(a.cond[set * a.set_stride_cond + ie]);
             if (active) a.g_cond[set * a.set_stride_cond + ie] = Net::grad_cond(p, acc, ce);
-            block_reduce_expand<Net, NC>(acc, ce, active ? 1.0 : 0.0, red_loss, red_fail, s_red, out, lane);
+            static_assert(kWide, "the resident-layer kernel has a factor table: 35 rows of LDS");
+            block_reduce_expand_wide<Net, NC>(acc, ce, active ? 1.0 : 0.0, red_loss, red_fail, smem, out, lane);
         } else {
         if (active) a.g_cond[set * a.set_stride_cond + i] = Net::grad_cond(p, acc, cst);
-        block_reduce_expand<Net, NC>(acc, cst, active ? 1.0 : 0.0, red_loss, red_fail, s_red, out, lane);
+        if constexpr (kWide) block_reduce_expand_wide<Net, NC>(acc, cst, active ? 1.0 : 0.0, red_loss, red_fail, smem, out, lane);
+        else block_reduce_expand<Net, NC>(acc, cst, active ? 1.0 : 0.0, red_loss, red_fail, s_red, out, lane);
         }
 #ifdef CUDE_WAVE_TIMING
         if (a.dbg != nullptr && lane == 0 && blockIdx.y == 0) {
@@ -477,6 +493,8 @@ static hipError_t launch_one(const CpepArgs& a, hipStream_t s) {
     const int64_t nblocks = a.blk_count > 0 ? a.blk_count : (a.N + kBlock - 1) / kBlock;   // (mixed launch: the first blocks)
     constexpr int TABROWS = Net::HAS_TAB ? 5 * Net::NCST : 0;
     constexpr int REDROWS = TABROWS > kRedRows ? TABROWS : kRedRows;
+    // (the gradient kernel's final reduction spreads over the first 5 + REDROWS rows, all of them, where those are at
+    // least kRedWideRows: cpep_kernel's kWide is derived from the same two constants)
     const size_t lds = sizeof(double) * (size_t)(5 + REDROWS + (GRAD ? a.T : 0)) * kBlock;
     const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
     if constexpr (GRAD && cpep_can_keep<Net>()) {

@@ -1353,6 +1353,47 @@ __device__ __forceinline__ void block_reduce_expand(const A& acc, const double (
     }
 }
 
+// block_reduce_expand for a kernel that has kRedWideRows rows of LDS to spare at that point (the fixed-step c-peptide
+// gradient kernels with a layer-1 factor table: cude_cpep.hip).  Every row of a chunk is written TWICE in a row, as 128
+// entries, so lane r finds the entries (l + r) & 63, l = 0 ... 63, of its row at the constant offsets l from one base
+// address, row start + r: the rotated index of block_reduce_expand costs three VALU instructions per read (add, and,
+// shift-add: 24 next to the 8 additions of a trip), at 16 active lanes, behind an LDS round trip each trip, at the very
+// end of the launch where nothing is left to overlap with.  Same entries in the same order: the sums are the same bits.
+// Row stride 128 doubles: lane r reads dword 258 r + 2 l -- banks 2 r + 2 l, distinct over the 16 reading lanes whether
+// the reads are issued one (64 banks) or two (32 banks) at a time; lanes write consecutive addresses.
+constexpr int kRedWideStride = 2 * kBlockLanes;
+constexpr int kRedWideRows = kRedRows * kRedWideStride / kBlockLanes;       // rows of kBlockLanes doubles: 32
+template <class Net, int NCST, class A>
+__device__ __forceinline__ void block_reduce_expand_wide(const A& acc, const double (&cst)[NCST], double keep,
+                                                         double extra0, double extra1, double* s_wide, double* out,
+                                                         int lane) {
+    constexpr int NV = Net::P + 2;
+    const double* const rd = s_wide + (lane & (kRedRows - 1)) * (kRedWideStride + 1);
+#pragma unroll
+    for (int c0 = 0; c0 < NV; c0 += kRedRows) {
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kRedRows; r++) {
+            const int q = c0 + r;
+            double v = 0.0;
+            if (q < Net::P) v = Net::grad_elem(q, acc, cst) * keep;
+            else if (q == Net::P) v = extra0;
+            else if (q == Net::P + 1) v = extra1;
+            if (q < NV) {
+                s_wide[r * kRedWideStride + lane] = v;
+                s_wide[r * kRedWideStride + kBlockLanes + lane] = v;
+            }
+        }
+        __syncthreads();
+        if (lane < kRedRows && c0 + lane < NV) {
+            double a = 0.0;
+#pragma unroll 16
+            for (int l = 0; l < kBlockLanes; l++) a += rd[l];
+            out[c0 + lane] = a;
+        }
+    }
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -250,13 +250,18 @@ CUDE_HD void m_tanh_vec(const double (&z)[W], double (&t)[W]) {
 }
 
 // t[j] = tanh(z[j]) given E[j] = exp(2 z[j]) (any sign of z): 1 - 2/(E+1), one shared reciprocal.
-// E is clamped to e^40 (tanh = 1 - 8.5e-18 there) so that the product of W <= 8 denominators stays finite.
+// The denominator E + 1 is clamped to e^40 (tanh = 1 - 8.5e-18 there) so that the product of W <= 8 denominators stays
+// finite.  The clamp sits BEHIND the add: E reaches this function through a select, a loop-carried value or an inline-asm
+// pin, the compiler cannot rule out a signalling NaN there and puts a canonicalising v_max_f64 x, x, x in front of a
+// clamp of E itself (one more VALU slot per unit and evaluation); the result of an add is known to be canonical.  Same
+// bits as min(E, e^40) + 1 for every E: one ulp of e^40 is 32, so e^40 + 1 == e^40; below the cap rounding is monotone,
+// so E + 1 <= e^40 and the min passes it; above it, for +Inf and for NaN (min returns the number) both give e^40.
 template <int W>
 CUDE_HD void m_tanh_from_exp(const double (&E)[W], double (&t)[W]) {
     static_assert(W <= 8, "batched reciprocal: product of denominators must stay below 1e308");
     double d[W], pre[W];
 #pragma unroll
-    for (int j = 0; j < W; j++) d[j] = fmin(E[j], 2.35385266837019985408e17) + 1.0;
+    for (int j = 0; j < W; j++) d[j] = fmin(E[j] + 1.0, 2.35385266837019985408e17);
     pre[0] = d[0];
 #pragma unroll
     for (int j = 1; j < W; j++) pre[j] = pre[j - 1] * d[j];
