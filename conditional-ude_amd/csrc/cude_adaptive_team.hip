@@ -23,8 +23,9 @@
 //     recursion itself, recursion + VJP back to back: 3.3 us per reversed step; now the longer of the two).  At the end
 //     the five accumulator sets are added up in wave order through LDS and wave 0 finishes as the one-wave kernel does.
 // Forward values (trajectories, SSE, accepted steps) are bit-identical to adaptive_unrolled_kernel -- the same arithmetic
-// in the same order; gradients differ by the association of the five partial sums (1e-15).
-#include "cude_adaptive.h"
+// in the same order; gradients differ by the association of the five partial sums (1e-15).  The error estimate that every
+// wave judges a trial step by is stated once, in cude_adaptive_step.h, with the reverse sweep's trip count and tape entries.
+#include "cude_adaptive_step.h"
 
 namespace cude {
 
@@ -35,17 +36,12 @@ __device__ __forceinline__ void team_barriers(int n) {
     for (int k = 0; k < n; k++) __syncthreads();
 }
 
-// stage adjoints of the step being reversed: registers, or one set of LDS rows per wave for the networks whose gradient
-// accumulators fill the register file (as cude_adaptive_unrolled.hip)
-template <class M, bool GRAD>
-constexpr bool team_adjoints_in_lds() { return GRAD && M::NetT::NACC > 40; }
-
 template <class M, bool GRAD>
 __global__ __launch_bounds__(kBlock*(kTeam + (GRAD ? 1 : 0))) void adaptive_team_kernel(typename M::Args a) {
     static_assert(!M::NEED_Y, "constant-Jacobian models only");
     constexpr int NS = M::NS;
     constexpr int P = M::P;
-    constexpr bool B_LDS = team_adjoints_in_lds<M, GRAD>();
+    constexpr bool B_LDS = adjoints_in_lds<M, GRAD>();
     using Net = typename M::NetT;
     // LDS: [kRedRows] reduction scratch | [2][kTeam] published network values | TG glucose rows, TG - 1 slope rows |
     // (GRAD) [NACC] accumulator rows for the sum over the waves, (wide networks) [7 NS] stage-adjoint rows of the scribe,
@@ -180,15 +176,7 @@ __global__ __launch_bounds__(kBlock*(kTeam + (GRAD ? 1 : 0))) void adaptive_team
                 for (int s = 0; s < NS; s++) ynew[s] = Y[s];
             }
         }
-        double ev[NS];
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            double e = 0.0;
-#pragma unroll
-            for (int j = 0; j < 7; j++) e = fma(TS_BT[j], K[j][s], e);
-            ev[s] = dt * e / fma(reltol, fmax(fabs(y[s]), fabs(ynew[s])), abstol);
-        }
-        const double est = rms(ev, NS);
+        const double est = tsit5_error_estimate<NS>(K, y, ynew, dt, abstol, reltol);
         const bool live = !done && !failed;
         if (live && !(fabs(est) <= 1.79769313486231570815e308)) failed = true;
         const bool accept = ctl.judge(est);
@@ -261,9 +249,7 @@ __global__ __launch_bounds__(kBlock*(kTeam + (GRAD ? 1 : 0))) void adaptive_team
         for (int q = 0; q < Net::NACC; q++) acc[q] = 0.0;
         double wsum = 0.0, carry = 0.0;
         const double gs = a.inv_n;
-        int n_max = n_acc;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) n_max = max(n_max, __shfl_xor(n_max, off, 64));
+        const int n_max = adaptive_wave_max(n_acc);
         double* const s_B = s_model + (2 * a.TG + Net::NACC) * kBlock;
         double* const s_pub = s_B + (B_LDS ? 7 * NS : 0) * kBlock;
         constexpr int kPub = 7;                    // five weights, h, t_n
@@ -275,13 +261,13 @@ __global__ __launch_bounds__(kBlock*(kTeam + (GRAD ? 1 : 0))) void adaptive_team
             int hi = n_out;
             double t_next = t;
             double h_ahead = 0.0;
-            if (n_max > 0) h_ahead = TAPE(n_max - 1 < n_acc ? n_max - 1 : (n_acc > 0 ? n_acc - 1 : 0));
+            if (n_max > 0) h_ahead = TAPE(tape_entry(n_max - 1, n_acc));
             int pb = 0;
 #pragma unroll 1
             for (int n = n_max - 1; n >= 0; n--) {
                 const bool on = n < n_acc;
                 const double h = h_ahead;
-                if (n > 0) h_ahead = TAPE(n - 1 < n_acc ? n - 1 : (n_acc > 0 ? n_acc - 1 : 0));
+                if (n > 0) h_ahead = TAPE(tape_entry(n - 1, n_acc));
                 const double tn = t_next - h;
                 if (on) t_next = tn;
                 StageRows<NS, B_LDS> B(s_B, lane);
@@ -407,7 +393,7 @@ static hipError_t launch_team(const typename M::Args& a, bool grad, hipStream_t 
     const int64_t nblocks = grad ? (a.N + kBlock - 1) / kBlock : launch_blocks(a);
     const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
     const size_t lds = sizeof(double) * (size_t)(kRedRows + 2 * kTeam + 2 * a.TG + (grad ? M::NetT::NACC + 2 * 7 + 2 : 0) +
-                                                 (grad && team_adjoints_in_lds<M, true>() ? 7 * M::NS : 0)) * kBlock;
+                                                 (grad && adjoints_in_lds<M, true>() ? 7 * M::NS : 0)) * kBlock;
     if (grad) {
         if (a.tape == nullptr || a.tape_cap < 1 || a.g_cond == nullptr) return hipErrorInvalidValue;
         // (networks with more than 64 accumulators spill heavily at the two waves per SIMD a team of five needs: they keep

@@ -1,7 +1,8 @@
 // Adaptive Tsit5 ensemble kernels for gfx950, stages unrolled -- the c-peptide models on the reference's sampling grid
 // (solve(model.problem, p = theta, saveat = timepoints), src/parameter-estimation.jl:59; src/saem.jl:52).
-//
-#include "cude_adaptive.h"
+// The error estimate of a trial step, the reverse sweep's trip count and tape entries and the "stage adjoints in LDS"
+// predicate are stated in cude_adaptive_step.h, shared with the team kernel and the suppression kernel.
+#include "cude_adaptive_step.h"
 
 namespace cude {
 
@@ -14,15 +15,8 @@ namespace cude {
 // no loop.  Same arithmetic in the same order: results are bit-identical to that kernel
 // (tests/test_gpu_adaptive_grad.py).  At 1e5 subjects, 2x4x4x1: forward 0.282 -> 0.195 ms, gradient 0.524 -> 0.369 ms.
 
-// stage adjoints of the step being reversed: registers, or LDS rows for the networks whose gradient accumulators fill
-// the register file
-#ifndef CUDE_ADAPT_BLDS_NACC
-#define CUDE_ADAPT_BLDS_NACC 40
-#endif
 template <class M, bool GRAD>
-constexpr bool unrolled_adjoints_in_lds() { return GRAD && M::NetT::NACC > CUDE_ADAPT_BLDS_NACC; }
-template <class M, bool GRAD>
-constexpr int unrolled_fixed_rows() { return kRedRows + (unrolled_adjoints_in_lds<M, GRAD>() ? 7 * M::NS : 0); }
+constexpr int unrolled_fixed_rows() { return kRedRows + (adjoints_in_lds<M, GRAD>() ? 7 * M::NS : 0); }
 
 template <class M, bool GRAD>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(adaptive_waves<M, GRAD>())))
@@ -30,7 +24,7 @@ void adaptive_unrolled_kernel(typename M::Args a) {
     static_assert(!M::NEED_Y, "constant-Jacobian models only");
     constexpr int NS = M::NS;
     constexpr int P = M::P;
-    constexpr bool B_LDS = unrolled_adjoints_in_lds<M, GRAD>();
+    constexpr bool B_LDS = adjoints_in_lds<M, GRAD>();
     constexpr int FIXED = unrolled_fixed_rows<M, GRAD>();
     // [kRedRows] reduction scratch, (large networks) 7 NS rows of stage adjoints, then TG glucose rows and TG - 1 slope rows
     extern __shared__ double smem[];
@@ -166,15 +160,7 @@ void adaptive_unrolled_kernel(typename M::Args a) {
                 for (int s = 0; s < NS; s++) ynew[s] = Y[s];
             }
         }
-        double ev[NS];
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            double e = 0.0;
-#pragma unroll
-            for (int j = 0; j < 7; j++) e = fma(TS_BT[j], K[j][s], e);
-            ev[s] = dt * e / fma(reltol, fmax(fabs(y[s]), fabs(ynew[s])), abstol);
-        }
-        const double est = rms(ev, NS);
+        const double est = tsit5_error_estimate<NS>(K, y, ynew, dt, abstol, reltol);
         const bool live = !done && !failed;
         if (live && !(fabs(est) <= 1.79769313486231570815e308)) failed = true;
         const bool accept = ctl.judge(est);
@@ -246,12 +232,10 @@ void adaptive_unrolled_kernel(typename M::Args a) {
         for (int s = 0; s < NS; s++) lam[s] = 0.0;
         const double gs = a.inv_n;
         int hi = n_out;
-        int n_max = n_acc;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) n_max = max(n_max, __shfl_xor(n_max, off, 64));
+        const int n_max = adaptive_wave_max(n_acc);
         double t_next = t;
         double h_ahead = 0.0;
-        if (n_max > 0) h_ahead = TAPE(n_max - 1 < n_acc ? n_max - 1 : (n_acc > 0 ? n_acc - 1 : 0));
+        if (n_max > 0) h_ahead = TAPE(tape_entry(n_max - 1, n_acc));
 #pragma unroll 1
         for (int n = n_max - 1; n >= 0; n--) {
             if (prio_shift > 0) {
@@ -260,7 +244,7 @@ void adaptive_unrolled_kernel(typename M::Args a) {
             }
             const bool on = n < n_acc;
             const double h = h_ahead;
-            if (n > 0) h_ahead = TAPE(n - 1 < n_acc ? n - 1 : (n_acc > 0 ? n_acc - 1 : 0));
+            if (n > 0) h_ahead = TAPE(tape_entry(n - 1, n_acc));
             const double tn = t_next - h;
             if (on) t_next = tn;
             StageRows<NS, B_LDS> B(s_B, lane);

@@ -12,7 +12,8 @@
 // losses, trajectories and accepted steps bit for bit, gradients to 3e-15 (the compiler fuses other multiply-add pairs).
 // 1e5 subjects, 4x3x3x3x3x3x1, one box: forward 0.468 -> 0.388 ms; gradient 1.814 ms (one body) -> 1.107 ms (unrolled,
 // stages re-run from y_n, stage rows in LDS) -> 0.819 ms (inputs kept on the tape).
-#include "cude_adaptive.h"
+// The error estimate of a trial step is stated in cude_adaptive_step.h, shared with the c-peptide kernels.
+#include "cude_adaptive_step.h"
 
 namespace cude {
 
@@ -133,15 +134,7 @@ void adaptive_unrolled_supp_kernel(SuppArgs a) {
                 for (int s = 0; s < NS; s++) ynew[s] = Y[s];
             }
         }
-        double ev[NS];
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            double e = 0.0;
-#pragma unroll
-            for (int j = 0; j < 7; j++) e = fma(TS_BT[j], K[j][s], e);
-            ev[s] = dt * e / fma(reltol, fmax(fabs(y[s]), fabs(ynew[s])), abstol);
-        }
-        const double est = rms(ev, NS);
+        const double est = tsit5_error_estimate<NS>(K, y, ynew, dt, abstol, reltol);
         const bool live = !done && !failed;
         if (live && !(fabs(est) <= 1.79769313486231570815e308)) failed = true;
         const bool accept = ctl.judge(est);
