@@ -205,6 +205,7 @@ const OptionEntry kOptions[] = {
     {"graph", "CUDE_NO_GRAPH", &Options::graph, true, true},
     {"graph_unroll", "CUDE_GRAPH_UNROLL", &Options::graph_unroll, false, true},
     {"prio_shift", "CUDE_PRIO_SHIFT", &Options::prio_shift, false, true},
+    {"prio_clock", "CUDE_PRIO_CLOCK", &Options::prio_clock, false, true},
     {"dense_chunk", "CUDE_DENSE_CHUNK", &Options::dense_chunk, false, false},
     {"dense_layout", "CUDE_DENSE_LAYOUT", &Options::dense_layout, false, false},
     {"refine_fused", "CUDE_REFINE_FUSED", &Options::refine_fused, false, false},

@@ -107,22 +107,54 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
     // other alone on the SIMD at the poor single-wave issue rate.  The two take turns at the higher priority instead --
     // by the parity of their hardware wave slot, every 2^prio_shift evaluations -- and finish together
     // (125 000 subjects: 0.582 -> 0.554 ms; no effect with one wave per SIMD, -2 % over many rounds: off there).
+    //
+    // WHEN the turns change (CpepArgs::prio_clock).  0: by each wave's own progress, as above.  The two waves are then
+    // complementary only while they are in step; once one is ahead there is a stretch in every period where both hold
+    // the same priority, age decides, and it decides for the same wave again.  k > 0: by the shader clock both waves
+    // read -- high priority while bit k of s_memtime differs from the slot parity -- so that the two are complementary
+    // at every instant, wherever each stands in its own sweep (125 000 subjects, timeline of the pairs: the earlier
+    // wave of a pair leaves 0.22 of the launch before the other with the progress-keyed turns, 0.026 with k = 17;
+    // 0.523 -> 0.494 ms, flat over k = 16 ... 19: profiles/prio_clock.txt).  The clock is requested next to seg[e] / phi[e] and
+    // comes back with them: one scalar round trip, no wait of its own.  One register carries both forms: prio > 0 is
+    // the progress-keyed shift, prio < 0 the clock bit under a set sign bit.  The adaptive kernels (cude_adaptive_body.h,
+    // cude_adaptive_unrolled.hip) carry the progress-keyed form only: their work per wave is data-dependent, and the
+    // host never hands them a clock bit (run_ensemble).
     const unsigned prio_par = GRAD ? (__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (3 << 11)) & 1u) : 0u;   // HW_ID.wave_id
-    const int prio_shift = GRAD ? a.prio_shift : 0;
+    const int prio = !GRAD || a.prio_shift <= 0 ? 0 : (a.prio_clock > 0 ? (int)(0x80000000u | (unsigned)a.prio_clock) : a.prio_shift);
+    // (every test looks at `prio` through an empty asm of its own, so that it stays the ONE scalar register the
+    // progress-keyed form had.  Left to itself the compiler keeps the outcome of the mode tests and the shift count in
+    // five more, across the loops, which the reverse sweep does not have: they come back as lane reads in the
+    // evaluation blocks.)
+    auto prio_now = [&]() {
+        int v = prio;
+        asm volatile("" : "+s"(v));
+        return v;
+    };
+    auto prio_by_clock = [&](uint64_t t) {
+        if (((unsigned)(t >> (prio_now() & 63)) ^ prio_par) & 1u) __builtin_amdgcn_s_setprio(2);
+        else __builtin_amdgcn_s_setprio(0);
+    };
     // (here, not at the top: the table's global read then travels with the subject's own loads -- one latency, not two)
     if constexpr (Net::USES_TANH) tanh_tab_init(lane, !Net::LDS_BIAS);
     Net::bias_init(a.nn + set * a.set_stride_nn, lane);
+    // (the baseline evaluation e = -1 has no scalar loads for the clock to travel with: its turn is set here, with a
+    // wait of its own, once per wave -- not in an else-arm of `if (e >= 0)` below, which changes how the loop's values
+    // merge: ~20 more register copies per evaluation, the whole launch 4 % slower in EVERY mode)
+    if (GRAD && prio_now() < 0) prio_by_clock(__builtin_amdgcn_s_memtime());
 #pragma unroll 1
     for (int e = -1; e < 5 * S; e++) {
-        if (GRAD && prio_shift > 0) {
-            if ((((unsigned)(e + 1) >> prio_shift) ^ prio_par) & 1u) __builtin_amdgcn_s_setprio(2);
+        if (const int pr = GRAD ? prio_now() : 0; pr > 0) {
+            if ((((unsigned)(e + 1) >> pr) ^ prio_par) & 1u) __builtin_amdgcn_s_setprio(2);
             else __builtin_amdgcn_s_setprio(0);
         }
         double xv = 0.0;
         bool tab = false;
         if (e >= 0) {
+            uint64_t clk = 0;
+            if (GRAD && prio_now() < 0) clk = __builtin_amdgcn_s_memtime();
             const int sg = seg[e];
             const double ph = phi[e];     // requested together with seg[e]: one scalar round trip, not two
+            if (GRAD && prio_now() < 0) prio_by_clock(clk);      // (the clock has come back with them)
             if (sg != cur_seg) {                 // wave-uniform: a handful of times per trajectory
                 cur_seg = sg;
                 g_lo = a.dG[(int64_t)sg * N + i];
@@ -289,8 +321,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
         // evaluations in reverse order; e = -1 is the baseline with weight -sum(w)
 #pragma unroll 1
         for (int e = 5 * S - 1; e >= -1; e--) {
-            if (prio_shift > 0) {
-                if ((((unsigned)(e + 1) >> prio_shift) ^ prio_par) & 1u) __builtin_amdgcn_s_setprio(2);
+            if (const int pr = prio_now(); pr > 0) {
+                if ((((unsigned)(e + 1) >> pr) ^ prio_par) & 1u) __builtin_amdgcn_s_setprio(2);
                 else __builtin_amdgcn_s_setprio(0);
             }
                 if (e >= 0 && s == 4) {
@@ -374,9 +406,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
             bool tab = false;
             typename Net::RS rs;
             if constexpr (kRW) Net::rw_request(p, rs);   // travels with seg[e] and phi[e]: one scalar round trip
-            if (e >= 0) {
+            if (e >= 0) {                                // (the baseline, last of the sweep, keeps the turn it inherits)
+                uint64_t clk = 0;
+                if (prio_now() < 0) clk = __builtin_amdgcn_s_memtime();
                 const int sg = seg[e];
                 const double ph = phi[e];
+                if (prio_now() < 0) prio_by_clock(clk);
                 if (sg != cur_seg) {
                     cur_seg = sg;
                     g_lo = a.dG[(int64_t)sg * N + i];

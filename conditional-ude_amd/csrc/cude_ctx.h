@@ -109,6 +109,8 @@ struct Options {
     int graph = 1;              // CUDE_NO_GRAPH
     int graph_unroll = 8;       // CUDE_GRAPH_UNROLL
     int prio_shift = -1;        // CUDE_PRIO_SHIFT (-1 = the rule in prio_shift_for)
+    int prio_clock = -1;        // CUDE_PRIO_CLOCK: the launches that alternate do so by their own progress (0) or by the shader clock,
+                                //   period 2^k cycles (k > 0); -1 = the rule in prio_clock_for
 };
 
 // Peer-write exchange (cude_comm.hip): this rank's mailbox, every rank's mailbox as mapped here, per-column sequence

@@ -107,6 +107,8 @@ struct CpepArgs {
     int64_t blk0, blk_count;
     int32_t prio_shift;      // one-lane gradient kernel: co-resident waves alternate issue priority every 2^prio_shift
                              // evaluations (0 = off); set by the host for single-round launches with two waves per SIMD
+    int32_t prio_clock;      // how the turns are timed where prio_shift > 0: 0 = by each wave's own progress (above; all the adaptive
+                             // kernels know), k > 0 = by bit k of the shader clock, i.e. every 2^k cycles (fixed-step kernel only)
     double* tape;            // adaptive gradient: [n_sets][tape_cap][N] step sizes dt_n of the accepted steps (+ T saved outputs)
     int32_t tape_cap;
     int32_t* tape_n;         // [N] accepted steps per subject of parameter set 0 (forward and gradient launches), or nullptr

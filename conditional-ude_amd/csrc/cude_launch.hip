@@ -383,6 +383,19 @@ int prio_shift_for(const cude_ctx* c, int64_t blocks) {
     return (c->slots_one >= 2 * c->half_slots && blocks > c->half_slots && blocks <= 2 * c->half_slots) ? 5 : 0;
 }
 
+// HOW the launches picked above take their turns (CpepArgs::prio_clock; option "prio_clock", ablation builds:
+// CUDE_PRIO_CLOCK): 0 = every 2^prio_shift evaluations of each wave's own progress, k > 0 = every 2^k cycles of the shader
+// clock the co-resident waves share.  Fixed-step c-peptide gradient kernel only: the adaptive kernels keep the
+// progress-keyed form, their work per wave being data-dependent (run_ensemble never hands them a clock bit).
+// Bit 17 = turns of 2^17 cycles, ~55 us, ~32 evaluations of the headline kernel: 125 000 subjects, 2-6-6-1 / 3 states,
+// kernel ms by k: 14 0.508, 15 0.498, 16 0.495, 17 0.495, 18 0.494, 19 0.495, 20 and up slower than no turns at all (a turn outlasts the sweep),
+// against 0.521 for the progress-keyed turns at their best common setting and 0.538 without (profiles/prio_clock.txt).
+constexpr int kPrioClockBit = 17;
+int prio_clock_for(const cude_ctx* c) {
+    const int k = c->opt.prio_clock >= 0 ? c->opt.prio_clock : kPrioClockBit;
+    return k < 62 ? k : 62;
+}
+
 // launches the ensemble kernel + second-stage reduction (+ all-reduce, + L2 term)
 // cond_ov / sse_ov: evaluate at other conditional parameters / write the per-subject SSE elsewhere and stop
 // after the ensemble kernels (used by the Metropolis E-step, which needs neither loss nor gradient).
@@ -452,7 +465,10 @@ int32_t run_ensemble(cude_ctx* c, bool grad, double* traj_dev, bool local_only, 
             a2.defer_chunk_sum = grad && c->blk0 == 0 && c->opt.fused_tail;      // (summed by the one tail launch below)
             HIP_TRY(cude::launch_cpep2(c->net, c->cfg.n_state, grad, a2, c->stream));
         } else {
-            if (grad && !adaptive(c)) a.prio_shift = prio_shift_for(c, c->nblocks);
+            if (grad && !adaptive(c)) {
+                a.prio_shift = prio_shift_for(c, c->nblocks);
+                a.prio_clock = a.prio_shift > 0 ? prio_clock_for(c) : 0;
+            }
             if (grad && adaptive(c)) {      // adaptive gradient kernel: at most two waves per SIMD (measured -4.8 %)
                 a.prio_shift = c->opt.prio_shift >= 0
                                    ? c->opt.prio_shift
@@ -760,6 +776,12 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
             a.n_sets = (int32_t)kn; a.set_stride_nn = stride_nn; a.set_stride_cond = stride_cond;
             if (adaptive(c) || gen) a.tape = c->ms_tape.p;     // (tape_n: the counts of set 0, for the re-ordering)
             if (gen) a.gen_acc = c->ms_gacc.p;
+            // (several sets are several rounds: no alternating issue priority by the library's rule; an explicit "prio_shift"
+            // option is honoured, so that the switch can be exercised on these launches too)
+            if (!adaptive(c) && !gen && c->opt.prio_shift > 0) {
+                a.prio_shift = c->opt.prio_shift;
+                a.prio_clock = prio_clock_for(c);
+            }
             HIP_TRY(cude::launch_cpep(c->net, c->cfg.n_state, true, a, c->stream));     // one-lane kernel: the sets fill the chip
         } else {
             cude::SuppArgs a = supp_args(c);

@@ -1,8 +1,13 @@
 """Per-wave timeline of one gradient launch (development aid).  Needs a library built with -DCUDE_WAVE_TIMING
 (tools/abl_so/wt.so): every wave records wall_clock64() at its start, after the forward sweep and at its end, plus
-its HW_ID / XCC_ID.  Prints the dispatch ramp (spread of start times), the wave lifetimes and the per-XCD picture.
+its HW_ID / XCC_ID.  Prints the dispatch ramp (spread of start times), the wave lifetimes and the per-XCD picture,
+then the waves that shared a SIMD pair by pair: how far apart the two finished, how long one of them had the SIMD to
+itself, and how the pairs' end times spread over the SIMDs of each XCD -- all as fractions of the launch (first start
+to last end), each with its median and 10 / 90 % quantiles, and once more on one line that starts with "summary:".
 
-usage: python tools/wave_timeline.py [N=125000] [variant=wt]
+usage: python tools/wave_timeline.py [N=125000] [variant=wt] [option=value ...]
+  option=value: cude_set_option before the launch, e.g. prio_shift=5 prio_clock=17 (clock-keyed issue priority),
+  prio_clock=0 (progress-keyed), prio_shift=0 (no alternation)
 """
 import ctypes as C
 import os
@@ -25,10 +30,21 @@ from cude.engine import Engine  # noqa: E402
 arch = (2, 6, 2)
 tp, G, cp, age, t2, bt, rng = o.synthetic_cpep_population(N)
 eng = Engine("cpep", arch, n_steps=30, n_state=3)
+for kv in sys.argv[3:]:
+    name, value = kv.split("=", 1)
+    eng.set_option(name, value)
 eng.set_population_cpep(tp, G, cp, age, t2)
-eng.set_params(o.glorot_params(arch, 1), bt)
+nn = o.glorot_params(arch, 1)
+eng.set_params(nn, bt)
+# the bench workload (bench.py, tools/quick_bench.py): observations = the device's own solve at the true conditional
+# parameters with 5 % noise, start at perturbed ones (the priority scheme's effect depends on the data: how many waves
+# leave the layer-1 table, and where)
+obs = eng.forward(want_traj=True)["traj"][0].T * (1 + 0.05 * rng.standard_normal((N, 5)))
+obs[:, 0] = cp[:, 0]
+eng.set_population_cpep(tp, G, obs, age, t2)
+eng.set_params(nn, bt + 0.3 * rng.standard_normal(N))
 eng.adam_init(1e-2)
-for _ in range(5):
+for _ in range(40):          # (the clock takes ~30 launches to settle: profiles/r02/clock_ramp.txt)
     eng.adam_step(want_loss=False)
 eng.set_kernel_timing(True)
 eng.adam_step(want_loss=False)
@@ -83,3 +99,49 @@ for x in range(8):
         slots = len(set(zip(se[m].tolist(), sh[m].tolist(), cu[m].tolist(), simd[m].tolist())))
         print(f"  XCC {x}: {m.sum()} waves on {slots} SIMDs, start max {start[m].max():.1f}, lifetime median "
               f"{np.median(life[m]):.1f} max {life[m].max():.1f}, end max {end[m].max():.1f}")
+
+# ---- the waves that shared a SIMD, pair by pair (fractions of the launch: first start -> last end)
+L = float(end.max())
+members = collections.defaultdict(list)
+for w, k in enumerate(simd_key):
+    members[k].append(w)
+pairs = np.array([v for v in members.values() if len(v) == 2], dtype=np.int64).reshape(-1, 2)
+n_lone = sum(1 for v in members.values() if len(v) == 1)
+n_more = sum(1 for v in members.values() if len(v) > 2)
+
+
+def q3(x):
+    """median and 10 / 90 % quantiles"""
+    lo, med, hi = np.quantile(x, [0.1, 0.5, 0.9])
+    return f"{med:.4f} ({lo:.4f} ... {hi:.4f})"
+
+
+print(f"SIMDs with two waves: {len(pairs)}, with one: {n_lone}, with more: {n_more}; launch {L:.1f} us")
+if len(pairs):
+    sa, sb = start[pairs[:, 0]], start[pairs[:, 1]]
+    ea, eb = end[pairs[:, 0]], end[pairs[:, 1]]
+    fin_diff = np.abs(ea - eb) / L
+    both = np.maximum(0.0, np.minimum(ea, eb) - np.maximum(sa, sb))
+    lone = ((ea - sa) + (eb - sb) - 2.0 * both) / L          # exactly one of the two resident
+    pair_end = np.maximum(ea, eb)
+    pair_xcc = xcc[pairs[:, 0]]
+    # which of the two left first: the one in the lower wave slot (HW_ID.wave_id), or the one dispatched first?
+    slot = hw & 0xF
+    low_first = np.where(slot[pairs[:, 0]] < slot[pairs[:, 1]], ea < eb, eb < ea)
+    early_first = np.where(sa <= sb, ea < eb, eb < ea)
+    print(f"  finishing-time difference / launch: median (10 ... 90 %) {q3(fin_diff)}, mean {fin_diff.mean():.4f}")
+    print(f"  one wave of the pair alone on the SIMD / launch: {q3(lone)}, mean {lone.mean():.4f} "
+          f"(start offsets included: {np.median(np.abs(sa - sb)) / L:.4f} median)")
+    print(f"  the wave in the lower slot finished first in {low_first.mean():.3f} of the pairs, "
+          f"the one dispatched first in {early_first.mean():.3f}")
+    print(f"  pair end / launch, all SIMDs: {q3(pair_end / L)}")
+    spreads = []
+    for x in sorted(set(pair_xcc.tolist())):
+        pe = pair_end[pair_xcc == x] / L
+        lo, hi = np.quantile(pe, [0.1, 0.9])
+        spreads.append(hi - lo)
+        print(f"    XCC {x}: {len(pe)} pairs, pair end / launch {q3(pe)}, 10-90 % spread {hi - lo:.4f}, last {pe.max():.4f}")
+    spreads = np.array(spreads)
+    print(f"summary: launch {L:.1f} us, kernel (events) {ms * 1e3:.1f} us, pairs {len(pairs)}, lone SIMD waves {n_lone}; "
+          f"finish diff {q3(fin_diff)}; lone share {q3(lone)}; pair end {q3(pair_end / L)}; "
+          f"pair-end 10-90 % spread per XCC {q3(spreads)}")
