@@ -527,6 +527,29 @@ hipError_t launch_profile_round(const ProfileArgs& a, const ProfileEnds& e, int 
 // ([kn][N] each) into the running minimum fmin [N] and its set index imin [N]; F as cude_profile_intervals rule 1
 hipError_t launch_best_of_sets(int64_t N, int k0, int kn, const double* sse, const double* x, double pw, double pc, double* fmin,
                                int32_t* imin, hipStream_t s);
+// per-subject marginal likelihoods (cude_marginal_likelihood, cude_marginal.hip; the numbered rules in include/cude.h)
+constexpr int kMarginalState = 6;                 // M, S0, S1, S2, S3, Q
+struct MarginalArgs {
+    int64_t N;
+    int32_t n_nodes;
+    const double* center;                         // [N]
+    const double* scale;                          // [N], or null: 1
+    const double* nodes; const double* log_weights;     // [n_nodes] (device memory), or both null: device draws
+    RngKey key;                                   // draws: key.step = first_step (node k draws at step first_step + k)
+    double c_K;                                   // draws: 0.5 log(2 pi) - log(n_nodes)
+    double ll_const, inv_2s2;                     // mh_tempered_ll's constants at temperature 1
+    double prior_mean, prior_sd, log_prior_sd;    // prior_sd = +Inf: no prior term
+    double* state;                                // [kMarginalState][N], kept between the chunks
+    int32_t* n_bad;                               // [N], likewise
+};
+// rows [k0, k0 + kn) of the points x [kn][N] and (draws) of the standard normals z [kn][N]
+hipError_t launch_marginal_points(const MarginalArgs& a, int k0, int kn, double* x, double* z, hipStream_t s);
+// nodes [k0, k0 + kn) into the running state, in node order; terms: [kn][N] or null; z: the draws' rows or null (the rule's)
+hipError_t launch_marginal_accumulate(const MarginalArgs& a, int k0, int kn, const double* sse, const double* x, const double* z,
+                                      double* terms, hipStream_t s);
+// outputs [N] each (null: not wanted); n_failed (one zeroed int32): subjects without a finite term
+hipError_t launch_marginal_finish(const MarginalArgs& a, double* logml, double* post_mean, double* post_var, double* post_sse,
+                                  double* ess, int32_t* n_failed, hipStream_t s);
 // exact order statistics and the sequential mean of every (subject, output time) column of a multi-set dense-output slab
 // (cude_predictive_bands, cude_predictive.hip).  slab: value of set k, column q at slab[k * set_stride + q * col_stride];
 // columns q in [0, n_cols) with q = j + Tc * (subject - first subject of the launch), j the time inside the chunk

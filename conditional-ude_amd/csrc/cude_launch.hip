@@ -1203,6 +1203,97 @@ int32_t cude_evaluate_conditional_sets(cude_ctx* c, int32_t n_sets, const double
     return CUDE_OK;
 }
 
+int32_t cude_marginal_likelihood(cude_ctx* c, int32_t n_nodes, const double* nodes, const double* log_weights,
+                                 int64_t first_step, const double* center, const double* scale, double sigma,
+                                 double prior_mean, double prior_sd, double* logml_out, double* post_mean_out,
+                                 double* post_var_out, double* post_sse_out, double* ess_out, int32_t* n_bad_out,
+                                 double* points_out, double* terms_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (!center && !c->have_cond) return fail(CUDE_ERR_STATE, "center is NULL and the conditional parameters are not set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_marginal_likelihood under stream capture");
+    if (n_nodes < 1 || n_nodes > 65536) return fail(CUDE_ERR_ARG, "n_nodes must lie in 1 ... 65536");
+    if ((nodes == nullptr) != (log_weights == nullptr)) return fail(CUDE_ERR_ARG, "pass both nodes and log_weights or neither");
+    const bool draws = nodes == nullptr;
+    if (!draws) {
+        for (int32_t k = 0; k < n_nodes; k++)
+            if (!std::isfinite(nodes[k]) || !std::isfinite(log_weights[k]))
+                return fail(CUDE_ERR_ARG, "nodes and log_weights must be finite");
+    }
+    if (first_step < 0) return fail(CUDE_ERR_ARG, "first_step must be >= 0");
+    if (!(sigma > 0) || !std::isfinite(sigma)) return fail(CUDE_ERR_ARG, "sigma must be finite and > 0");
+    if (!(prior_sd > 0)) return fail(CUDE_ERR_ARG, "prior_sd must be > 0 (+Inf: no prior term)");
+    if (!std::isfinite(prior_mean)) return fail(CUDE_ERR_ARG, "prior_mean must be finite");
+    if (!logml_out && !post_mean_out && !post_var_out && !post_sse_out && !ess_out && !n_bad_out && !points_out && !terms_out)
+        return fail(CUDE_ERR_ARG, "no output requested");
+    const int64_t N = c->N;
+    const int64_t chunk = profile_chunk_sets(c, n_nodes);
+    DevBuf<double> d_x, d_z, d_sse, d_terms, d_part, d_rule, d_in, d_state, d_out;
+    DevBuf<int32_t> d_bad;              // [N] bad nodes, then the number of subjects without a finite term
+    HIP_TRY(d_x.resize((size_t)chunk * N));
+    HIP_TRY(d_sse.resize((size_t)chunk * N));
+    if (draws) HIP_TRY(d_z.resize((size_t)chunk * N));
+    if (terms_out) HIP_TRY(d_terms.resize((size_t)chunk * N));
+    HIP_TRY(d_state.resize((size_t)cude::kMarginalState * N));
+    HIP_TRY(d_out.resize((size_t)5 * N));
+    HIP_TRY(d_bad.resize((size_t)N + 1));
+    if ((rc = reserve_sets_forward(c, chunk, false, d_part))) return rc;
+    cude::MarginalArgs m{};
+    m.N = N; m.n_nodes = n_nodes;
+    if (!draws) {
+        HIP_TRY(d_rule.resize((size_t)2 * n_nodes));
+        HIP_TRY(hipMemcpyAsync(d_rule.p, nodes, n_nodes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_rule.p + n_nodes, log_weights, n_nodes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        m.nodes = d_rule.p; m.log_weights = d_rule.p + n_nodes;
+    }
+    if (center || scale) HIP_TRY(d_in.resize((size_t)2 * N));
+    m.center = c->cond.p;
+    if (center) {
+        HIP_TRY(hipMemcpyAsync(d_in.p, center, N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        m.center = d_in.p;
+    }
+    if (scale) {
+        HIP_TRY(hipMemcpyAsync(d_in.p + N, scale, N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        m.scale = d_in.p + N;
+    }
+    // the stream's key at first_step; the context's own position (rng_step) is neither read nor advanced
+    m.key = cude::RngKey{c->rng_seed, c->rng_offset, first_step};
+    m.c_K = 0.91893853320467274178 - std::log((double)n_nodes);   // 0.5 log(2 pi) - log K
+    m.ll_const = -(c->T / 2.0) * std::log(sigma * sigma);        // cude_mh_chain's
+    m.inv_2s2 = 1.0 / (2.0 * sigma * sigma);
+    m.prior_mean = prior_mean; m.prior_sd = prior_sd;
+    m.log_prior_sd = std::isfinite(prior_sd) ? std::log(prior_sd) : 0.0;
+    m.state = d_state.p; m.n_bad = d_bad.p;
+    SetsForward fwd;                                      // one network, kn sets of per-subject values
+    fwd.cond = d_x.p; fwd.nn = c->nn.p; fwd.sse = d_sse.p; fwd.partials = d_part.p;
+    for (int64_t k0 = 0; k0 < n_nodes; k0 += chunk) {
+        const int64_t kn = std::min<int64_t>(chunk, n_nodes - k0);
+        HIP_TRY(cude::launch_marginal_points(m, (int)k0, (int)kn, d_x.p, d_z.p, c->stream));
+        fwd.n_sets = (int)kn;
+        if ((rc = forward_sets(c, fwd))) return rc;
+        HIP_TRY(cude::launch_marginal_accumulate(m, (int)k0, (int)kn, d_sse.p, d_x.p, d_z.p, d_terms.p, c->stream));
+        if (points_out)
+            HIP_TRY(hipMemcpyAsync(points_out + k0 * N, d_x.p, kn * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (terms_out)
+            HIP_TRY(hipMemcpyAsync(terms_out + k0 * N, d_terms.p, kn * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        // (the chunk buffers are the next chunk's too: copies to pageable memory are staged in stream order)
+    }
+    HIP_TRY(hipMemsetAsync(d_bad.p + N, 0, sizeof(int32_t), c->stream));
+    double* const o = d_out.p;
+    HIP_TRY(cude::launch_marginal_finish(m, o, o + N, o + 2 * N, o + 3 * N, o + 4 * N, d_bad.p + N, c->stream));
+    double* const outs[5] = {logml_out, post_mean_out, post_var_out, post_sse_out, ess_out};
+    for (int q = 0; q < 5; q++)
+        if (outs[q]) HIP_TRY(hipMemcpyAsync(outs[q], o + (size_t)q * N, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_bad_out) HIP_TRY(hipMemcpyAsync(n_bad_out, d_bad.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    int32_t failed = 0;
+    HIP_TRY(hipMemcpyAsync(&failed, d_bad.p + N, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_failed = failed;
+    return CUDE_OK;
+}
+
 int32_t cude_sensitivity(cude_ctx* c, double* sens, double* info, double* score, double* sse) {
     int32_t rc = bind(c);
     if (rc) return rc;

@@ -1452,6 +1452,91 @@ def individual_effects(models, timepoints, cpeptide_data, saem_result, *, n_samp
     return out
 
 
+# ----------------------------------------------------------------------------- marginal likelihood
+def gauss_hermite_rule(Q):
+    """(nodes z, log_weights a) of the Q-point Gauss-Hermite rule in the form cude_marginal_likelihood takes: with the
+    physicists' rule (t_k, w_k) for the weight exp(-t^2), z = sqrt(2) t and a = log w + t^2 + log(2) / 2, so that
+    integral f(x) dx ~ s sum_k exp(a_k) f(m + s z_k) (the factor s is rule 4's log scale).  Exact for f = a Gaussian
+    density of mean m and standard deviation s times a polynomial of degree < 2Q; Q = 1 is the Laplace value
+    f(m) s sqrt(2 pi)."""
+    t, w = np.polynomial.hermite.hermgauss(int(Q))
+    return math.sqrt(2.0) * t, np.log(w) + t * t + 0.5 * math.log(2.0)
+
+
+def grid_rule(lo, hi, n):
+    """(nodes, log_weights) of the trapezoid rule on n >= 2 equidistant points of [lo, hi], for center 0 and scale 1: the
+    route that does not depend on where a subject's posterior mass lies."""
+    n = int(n)
+    if n < 2 or not hi > lo:
+        raise ValueError("grid_rule: need n >= 2 and hi > lo")
+    x = np.linspace(lo, hi, n)
+    w = np.full(n, (hi - lo) / (n - 1))
+    w[0] = w[-1] = 0.5 * w[0]
+    return x, np.log(w)
+
+
+def marginal_likelihood(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, method="quadrature",
+                        n_nodes=33, grid_halfwidth=8.0, lower=-6.0, upper=4.0, first_step=0, seed=None, normalized=False,
+                        n_steps=None):
+    """Every subject's marginal log-likelihood log integral exp(individual_log_likelihood(eta) + logpdf(Normal(prior_mean,
+    omega), eta)) d eta (src/saem.jl:55-66) with the network frozen, on the device (cude_marginal_likelihood).
+    method = "quadrature": the n_nodes-point Gauss-Hermite rule centred at every subject's MAP -- refine_conditional with
+    penalty weight (sigma / omega)^2 from betas (None: an 81-point scan over [lower, upper] first) -- with the Laplace
+    scale sigma / sqrt(info + (sigma / omega)^2).  "importance": n_nodes device draws from that normal (steps first_step
+    ... of the device stream; seed: set_rng first), self-normalised.  "grid": the trapezoid rule on n_nodes points over
+    prior_mean -/+ grid_halfwidth omega, which needs no centre and misses no mode inside the range.
+    Returns a namespace: logml, post_mean, post_var, post_sse, ess (N,), n_bad (N,) int32, center, scale (N,), and total =
+    the sum of logml in subject order.  The likelihood follows the reference's convention (no 2 pi constant);
+    normalized = True adds -(T/2) log(2 pi) per subject."""
+    if method not in ("quadrature", "grid", "importance"):
+        raise ValueError('method must be "quadrature", "grid" or "importance"')
+    sym = isinstance(models[0], CPeptideODEModel)
+    pop = _population(models, timepoints, cpeptide_data, n_steps, cond_space="raw" if sym else "log")
+    eng, N = pop.engine, pop.N
+    eng.set_params(pop.shared if sym and nn is None else nn, None)
+    sigma, omega, prior_mean = float(sigma), float(omega), float(prior_mean)
+    if method == "grid":
+        z, a = grid_rule(prior_mean - grid_halfwidth * omega, prior_mean + grid_halfwidth * omega, n_nodes)
+        center, scale = np.zeros(N), np.ones(N)
+        r = eng.marginal_likelihood(sigma, prior_mean, omega, nodes=z, log_weights=a, center=center)
+    else:
+        pw = (sigma / omega) ** 2
+        start = None if betas is None else np.asarray(betas, dtype=np.float64).reshape(-1)[:N]
+        center, _, _, info = _fit_box(eng, lower, upper, 81 if start is None else 0, 48, "newton", start=start,
+                                      penalty_weight=pw, penalty_center=prior_mean)
+        scale = sigma / np.sqrt(info + pw)
+        if method == "quadrature":
+            z, a = gauss_hermite_rule(n_nodes)
+            r = eng.marginal_likelihood(sigma, prior_mean, omega, nodes=z, log_weights=a, center=center, scale=scale)
+        else:
+            if seed is not None:
+                eng.set_rng(seed)
+            r = eng.marginal_likelihood(sigma, prior_mean, omega, n_draws=n_nodes, first_step=first_step, center=center,
+                                        scale=scale)
+    logml = r["logml"] - 0.5 * pop.T * math.log(2.0 * math.pi) if normalized else r["logml"]
+    return SimpleNamespace(logml=logml, total=float(np.add.accumulate(logml)[-1]), post_mean=r["post_mean"],
+                           post_var=r["post_var"], post_sse=r["post_sse"], ess=r["ess"], n_bad=r["n_bad"], center=center,
+                           scale=scale)
+
+
+def information_criteria(total_logml, n_params, n_subjects, n_obs):
+    """AIC and BIC from a population's marginal log-likelihood (marginal_likelihood(...).total, with normalized = True
+    when models of different error structure are compared): dict(aic = -2 logL + 2 p, bic = -2 logL + p log(n_subjects
+    n_obs) -- the penalty counts every observation --, bic_subjects = -2 logL + p log(n_subjects), the count of independent
+    units some authors prefer for mixed-effects models)."""
+    dev = -2.0 * float(total_logml)
+    return {"aic": dev + 2.0 * n_params, "bic": dev + n_params * math.log(n_subjects * n_obs),
+            "bic_subjects": dev + n_params * math.log(n_subjects)}
+
+
+def em_updates(post_mean, post_var, post_sse, n_obs):
+    """The closed-form EM updates from the posterior moments cude_marginal_likelihood leaves: (sigma2, mu, omega2) with
+    sigma2 = sum_i E[SSE_i] / (N n_obs), mu = mean_i E[eta_i], omega2 = mean_i (Var[eta_i] + (E[eta_i] - mu)^2)."""
+    m, v, s = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (post_mean, post_var, post_sse))
+    mu = float(np.mean(m))
+    return float(np.sum(s) / (m.size * n_obs)), mu, float(np.mean(v + (m - mu) ** 2))
+
+
 # ----------------------------------------------------------------------------- symbolic (Michaelis-Menten) model
 def train_symbolic(models, timepoints, cpeptide_data, *, lower=0.0, upper=1000.0, n_steps=None, method="search"):
     """The per-subject loop of c-peptide/03-symreg.jl:94-106: minimise loss_sigma over (k, sigma) with

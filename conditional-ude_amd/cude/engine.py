@@ -431,6 +431,38 @@ class Engine:
                                                        float(penalty_center), _ptr(sse), _ptr(idx), _ptr(obj)))
         return {"index": idx, "objective": obj, "sse": sse}
 
+    def marginal_likelihood(self, sigma, prior_mean=0.0, prior_sd=np.inf, *, nodes=None, log_weights=None, n_draws=None,
+                            first_step=0, center=None, scale=None, want_points=False, want_terms=False):
+        """Per-subject marginal log-likelihoods on the device (cude_marginal_likelihood): log of the integral over the
+        random effect of exp(log-likelihood + log prior), by the rule (nodes, log_weights) (K,) at x = center + scale *
+        nodes, or -- nodes and log_weights None, n_draws = K -- by self-normalised importance sampling from
+        Normal(center, scale^2) with the device stream's normals of steps first_step ... (rng_draws' bits; the stream
+        position is left alone).  center (N,) -- None: the context's conditional parameters; scale (N,) -- None: 1.
+        Returns dict(logml, post_mean, post_var, post_sse, ess (N,) doubles; n_bad (N,) int32; points, terms (K, N) --
+        None unless wanted).  A subject with no finite term: logml -Inf, the moments NaN, counted by n_failed()."""
+        z = None if nodes is None else _f64(nodes).reshape(-1)
+        a = None if log_weights is None else _f64(log_weights).reshape(-1)
+        if z is None and a is None:
+            if n_draws is None:
+                raise ValueError("n_draws is required when the points are drawn on the device")
+            K = int(n_draws)
+        else:                                   # (one of the two alone: the library's CUDE_ERR_ARG)
+            if z is not None and a is not None and z.size != a.size:
+                raise ValueError("nodes and log_weights differ in length")
+            K = (z if z is not None else a).size
+        cen = None if center is None else np.ascontiguousarray(np.broadcast_to(_f64(center), (self.N,)))
+        scl = None if scale is None else np.ascontiguousarray(np.broadcast_to(_f64(scale), (self.N,)))
+        out = {k: np.empty(self.N) for k in ("logml", "post_mean", "post_var", "post_sse", "ess")}
+        out["n_bad"] = np.empty(self.N, dtype=np.int32)
+        rows = max(K, 0)
+        out["points"] = np.empty((rows, self.N)) if want_points else None
+        out["terms"] = np.empty((rows, self.N)) if want_terms else None
+        check(self._lib.cude_marginal_likelihood(
+            self._h, K, _ptr(z), _ptr(a), int(first_step), _ptr(cen), _ptr(scl), float(sigma), float(prior_mean),
+            float(prior_sd), _ptr(out["logml"]), _ptr(out["post_mean"]), _ptr(out["post_var"]), _ptr(out["post_sse"]),
+            _ptr(out["ess"]), _ptr(out["n_bad"]), _ptr(out["points"]), _ptr(out["terms"])))
+        return out
+
     def fit_conditional(self, lower, upper, n_grid=41, n_iters=48, penalty_weight=0.0, penalty_center=0.0):
         """All subjects' 1-D fits of the conditional parameter with the shared parameters frozen, on the device:
         argmin_x SSE_i(x) + penalty_weight (x - penalty_center)^2 over [lower, upper] -> (x[N], objective[N], sse[N])."""

@@ -22,13 +22,15 @@ module CUDEHip
 
 using Random: AbstractRNG, randn, rand, randperm
 using Statistics: mean, var
+using LinearAlgebra: SymTridiagonal, eigen
 
 export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEModel, CPeptideConditionalCovariateUDEModel,
        CPeptideUDEModel,
        loss, loss_sigma, loss_and_gradient!, train, train_with_sigma, evaluate_model, likelihood_profile,
        profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
-       sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals
+       sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
+       marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates
 
 const LIB = get(ENV, "CUDE_HIP_LIB", "libcude_hip.so")
 const MODEL_CPEP, MODEL_SUPP, MODEL_CPEP_SYM = Int32(0), Int32(1), Int32(2)
@@ -302,6 +304,30 @@ function evaluate_conditional_sets(c::Ctx, cond_sets::Matrix{Float64}; penalty_w
         (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
         c.h, K, cond_sets, penalty_weight, penalty_center, sse, idx, obj))
     idx .+ Int32(1), obj, sse
+end
+
+# per-subject marginal log-likelihoods on the device (cude_marginal_likelihood): log ∫ exp(ll(η) + log N(η; prior_η, Ω)) dη by
+# the rule (nodes, log_weights) at x = center + scale * nodes, or -- nodes = log_weights = nothing, n_draws = K -- by
+# self-normalised importance sampling from N(center, scale²) with the device stream's normals of steps first_step ...
+# (rng_draws' bits; the stream position is left alone).  center = nothing: the context's conditional parameters; scale =
+# nothing: 1.  Returns (logml, post_mean, post_var, post_sse, ess, n_bad, points N×K, terms N×K)
+function marginal_likelihood(c::Ctx, σ, prior_η, Ω; nodes = nothing, log_weights = nothing, n_draws = 0, first_step = 0,
+                             center = nothing, scale = nothing)
+    z = nodes === nothing ? nothing : Vector{Float64}(vec(nodes))
+    a = log_weights === nothing ? nothing : Vector{Float64}(vec(log_weights))
+    K = z === nothing ? (a === nothing ? Int(n_draws) : length(a)) : length(z)
+    cen = center === nothing ? nothing : Vector{Float64}(vec(center))
+    scl = scale === nothing ? nothing : Vector{Float64}(vec(scale))
+    logml = Vector{Float64}(undef, c.N); pmean = similar(logml); pvar = similar(logml); psse = similar(logml)
+    ess = similar(logml); n_bad = Vector{Int32}(undef, c.N)
+    points = Matrix{Float64}(undef, c.N, max(K, 0)); terms = similar(points)
+    GC.@preserve z a cen scl logml pmean pvar psse ess n_bad points terms check(ccall((:cude_marginal_likelihood, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Float64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+        c.h, Int32(K), z === nothing ? C_NULL : pointer(z), a === nothing ? C_NULL : pointer(a), Int64(first_step),
+        cen === nothing ? C_NULL : pointer(cen), scl === nothing ? C_NULL : pointer(scl), Float64(σ), Float64(prior_η),
+        Float64(Ω), logml, pmean, pvar, psse, ess, n_bad, points, terms))
+    logml, pmean, pvar, psse, ess, n_bad, points, terms
 end
 
 adam_init!(c::Ctx, η; β1 = 0.9, β2 = 0.999, ϵ = 1e-8) =
@@ -1123,6 +1149,74 @@ function compute_individual_maps(p_individuals, p_neural, individuals, σ, Ω, n
                          method == newton ? 0 : 81, method; start = p_individuals, penalty_weight = (σ / Ω)^2,
                          penalty_center = prior_individual)
     x
+end
+
+# ----------------------------------------------------------------------------------------------- marginal likelihood
+# (nodes z, log_weights a) of the Q-point Gauss-Hermite rule as cude_marginal_likelihood takes it: the physicists' rule
+# (tₖ, wₖ) by Golub-Welsch, z = √2 t, a = log w + t² + log(2)/2; Q = 1 is the Laplace value f(m) s √(2π)
+function gauss_hermite_rule(Q::Integer)
+    Q == 1 && return [0.0], [0.5 * log(2π)]
+    E = eigen(SymTridiagonal(zeros(Q), [sqrt(k / 2) for k in 1:Q-1]))
+    t = E.values
+    w = sqrt(π) .* E.vectors[1, :] .^ 2
+    sqrt(2.0) .* t, log.(w) .+ t .^ 2 .+ 0.5 * log(2.0)
+end
+
+# the trapezoid rule on n equidistant points of [lo, hi] as (nodes, log_weights), for center 0 and scale 1
+function grid_rule(lo, hi, n::Integer)
+    (n >= 2 && hi > lo) || error("grid_rule: need n >= 2 and hi > lo")
+    x = collect(Float64, range(lo, stop = hi, length = n))
+    w = fill((hi - lo) / (n - 1), n)
+    w[1] = w[n] = 0.5 * w[1]
+    x, log.(w)
+end
+
+# every individual's marginal log-likelihood with the network frozen (cude_marginal_likelihood).  method = :quadrature: the
+# n_nodes-point Gauss-Hermite rule at every MAP (refine_conditional with penalty weight (σ/Ω)² from betas; nothing: an
+# 81-point scan first) with the Laplace scale σ / √(info + (σ/Ω)²); :importance: n_nodes device draws from that normal;
+# :grid: the trapezoid rule on n_nodes points over prior_mean ∓ grid_halfwidth Ω.  The likelihood follows the reference's
+# convention (no 2π constant); normalized = true adds -(T/2) log 2π per individual.  total = the sum in subject order
+function marginal_likelihood(betas, p_neural, individuals, network::Chain, σ, prior_mean, Ω; method = :quadrature,
+                             n_nodes = 33, grid_halfwidth = 8.0, lower = -6.0, upper = 4.0, first_step = 0, seed = nothing,
+                             normalized = false, n_steps = nothing)
+    method in (:quadrature, :grid, :importance) || error("method must be :quadrature, :grid or :importance")
+    c = individuals_population(individuals, network; n_steps = n_steps)
+    set_params!(c, p_neural, nothing)
+    if method == :grid
+        z, a = grid_rule(prior_mean - grid_halfwidth * Ω, prior_mean + grid_halfwidth * Ω, n_nodes)
+        center = zeros(c.N); scale = ones(c.N)
+        r = marginal_likelihood(c, σ, prior_mean, Ω; nodes = z, log_weights = a, center = center)
+    else
+        pw = (σ / Ω)^2
+        center, _, _, info = fit_box(c, lower, upper, betas === nothing ? 81 : 0, newton;
+                                     start = betas === nothing ? nothing : Vector{Float64}(vec(betas)), penalty_weight = pw,
+                                     penalty_center = prior_mean)
+        scale = σ ./ sqrt.(info .+ pw)
+        if method == :quadrature
+            z, a = gauss_hermite_rule(n_nodes)
+            r = marginal_likelihood(c, σ, prior_mean, Ω; nodes = z, log_weights = a, center = center, scale = scale)
+        else
+            seed === nothing || set_rng!(c, seed)
+            r = marginal_likelihood(c, σ, prior_mean, Ω; n_draws = n_nodes, first_step = first_step, center = center,
+                                    scale = scale)
+        end
+    end
+    logml = normalized ? r[1] .- 0.5 * c.T * log(2π) : r[1]
+    (logml = logml, total = foldl(+, logml), post_mean = r[2], post_var = r[3], post_sse = r[4], ess = r[5], n_bad = r[6],
+     center = center, scale = scale)
+end
+
+# AIC and BIC from a population's marginal log-likelihood: bic penalises with the count of all observations, bic_subjects
+# with the count of individuals
+function information_criteria(total_logml, n_params, n_subjects, n_obs)
+    dev = -2.0 * total_logml
+    (aic = dev + 2.0 * n_params, bic = dev + n_params * log(n_subjects * n_obs), bic_subjects = dev + n_params * log(n_subjects))
+end
+
+# the closed-form EM updates from the posterior moments: (σ², μ, Ω²)
+function em_updates(post_mean, post_var, post_sse, n_obs)
+    μ = mean(post_mean)
+    sum(post_sse) / (length(post_mean) * n_obs), μ, mean(post_var .+ (post_mean .- μ) .^ 2)
 end
 
 # SAEM(individuals, initial_neural_params, network; ...) (:134-237): the E-step of all individuals is one call
