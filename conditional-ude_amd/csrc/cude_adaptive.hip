@@ -39,7 +39,9 @@ static hipError_t launch_adaptive(const typename M::Args& a, int extra_rows, boo
     const size_t lds = sizeof(double) * (size_t)(adaptive_rows<M>(grad) + extra_rows) * kBlock;
     const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
     if (grad && (a.tape == nullptr || a.tape_cap < 1 || a.g_cond == nullptr)) return hipErrorInvalidValue;
-    if (grad) {
+    if (grad && a.lane_rows != nullptr) {
+        hipLaunchKernelGGL((adaptive_kernel<M, IS_CPEP, true, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
+    } else if (grad) {
         hipLaunchKernelGGL((adaptive_kernel<M, IS_CPEP, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     } else {
         hipLaunchKernelGGL((adaptive_kernel<M, IS_CPEP, false>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);

@@ -15,7 +15,8 @@ constexpr int adaptive_rows(bool grad) {
     return KROWS + (grad ? 7 * M::NS * (M::NEED_Y ? 2 : 1) : 0);
 }
 
-template <class M, bool IS_CPEP, bool GRAD>
+// ROWS (gradient only): the lanes' own gradient rows also go to Args::lane_rows; a kernel of its own, as cpep_kernel's
+template <class M, bool IS_CPEP, bool GRAD, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(adaptive_waves<M, GRAD>())))
 void adaptive_kernel(typename M::Args a) {
     constexpr int NS = M::NS;
@@ -481,6 +482,7 @@ void adaptive_kernel(typename M::Args a) {
         m.finish_grad(a, i, set, acc, wsum, carry, cst);
         __syncthreads();                   // the reduction scratch aliases s_K
         if (active) a.g_cond[set * a.set_stride_cond + i] = Net::grad_cond(m.p, acc, cst);
+        if constexpr (ROWS) store_lane_rows<Net, M::NCST>(acc, cst, active, a.lane_rows + (set * P) * a.N + i, a.N);
         block_reduce_expand<Net, M::NCST>(acc, cst, active ? 1.0 : 0.0, active ? sse : 0.0, (active && bad) ? 1.0 : 0.0,
                                           smem, out, lane);
 #undef BROW

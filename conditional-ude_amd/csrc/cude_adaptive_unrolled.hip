@@ -18,7 +18,8 @@ namespace cude {
 template <class M, bool GRAD>
 constexpr int unrolled_fixed_rows() { return kRedRows + (adjoints_in_lds<M, GRAD>() ? 7 * M::NS : 0); }
 
-template <class M, bool GRAD>
+// ROWS (gradient only): the lanes' own gradient rows also go to Args::lane_rows; a kernel of its own, as cpep_kernel's
+template <class M, bool GRAD, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(adaptive_waves<M, GRAD>())))
 void adaptive_unrolled_kernel(typename M::Args a) {
     static_assert(!M::NEED_Y, "constant-Jacobian models only");
@@ -313,6 +314,7 @@ void adaptive_unrolled_kernel(typename M::Args a) {
         m.finish_grad(a, i, set, acc, wsum, carry, cst);
         __syncthreads();
         if (active) a.g_cond[set * a.set_stride_cond + i] = Net::grad_cond(m.p, acc, cst);
+        if constexpr (ROWS) store_lane_rows<Net, M::NCST>(acc, cst, active, a.lane_rows + (set * P) * a.N + i, a.N);
         block_reduce_expand<Net, M::NCST>(acc, cst, active ? 1.0 : 0.0, active ? sse : 0.0, (active && bad) ? 1.0 : 0.0,
                                           smem, out, lane);
     }
@@ -328,7 +330,10 @@ static hipError_t launch_unrolled(const typename M::Args& a, bool grad, hipStrea
                                                   2 * a.TG) * kBlock;
     if (grad) {
         if (a.tape == nullptr || a.tape_cap < 1 || a.g_cond == nullptr) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((adaptive_unrolled_kernel<M, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
+        if (a.lane_rows != nullptr)
+            hipLaunchKernelGGL((adaptive_unrolled_kernel<M, true, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
+        else
+            hipLaunchKernelGGL((adaptive_unrolled_kernel<M, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     } else {
         hipLaunchKernelGGL((adaptive_unrolled_kernel<M, false>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     }

@@ -17,7 +17,8 @@
 
 namespace cude {
 
-template <class M, bool GRAD>
+// ROWS (gradient only): the lanes' own gradient rows also go to Args::lane_rows; a kernel of its own, as cpep_kernel's
+template <class M, bool GRAD, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void adaptive_unrolled_supp_kernel(SuppArgs a) {
     static_assert(M::NEED_Y && M::NS == 3, "the suppression model");
@@ -327,6 +328,7 @@ void adaptive_unrolled_supp_kernel(SuppArgs a) {
         m.finish_grad(a, i, set, acc, wsum, 0.0, cst);
         __syncthreads();
         if (active) a.g_cond[set * a.set_stride_cond + i] = Net::grad_cond(m.p, acc, cst);
+        if constexpr (ROWS) store_lane_rows<Net, M::NCST>(acc, cst, active, a.lane_rows + (set * P) * a.N + i, a.N);
         block_reduce_expand<Net, M::NCST>(acc, cst, active ? 1.0 : 0.0, active ? sse : 0.0, (active && bad) ? 1.0 : 0.0,
                                           smem, out, lane);
     }
@@ -341,7 +343,10 @@ static hipError_t launch_unrolled_supp(const SuppArgs& a, bool grad, hipStream_t
     const size_t lds = sizeof(double) * (size_t)kRedRows * kBlock;      // the final reduction's scratch
     if (grad) {
         if (a.tape == nullptr || a.tape_cap < 1 || a.g_cond == nullptr) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((adaptive_unrolled_supp_kernel<M, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
+        if (a.lane_rows != nullptr)
+            hipLaunchKernelGGL((adaptive_unrolled_supp_kernel<M, true, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
+        else
+            hipLaunchKernelGGL((adaptive_unrolled_supp_kernel<M, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     } else {
         hipLaunchKernelGGL((adaptive_unrolled_supp_kernel<M, false>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     }

@@ -28,7 +28,9 @@ namespace cude {
 // (2-6-6-1, 8.5 KB per subject each way): the reverse evaluation drops from 375 to ~215 VALU instructions, but the launch
 // becomes HBM-bound at ~3.7 TB/s of mixed streaming -- 125 000 subjects 0.564 -> 0.578 ms, 1e6 4.18 -> 4.64 ms, 1e5 (mixed
 // launch) 0.492 -> 0.476 ms, 65 536 unchanged (profiles/r03/keep_activations.txt).  Not enabled: CUDE_CPEP_KEEP=1 selects it.
-template <class Net, int NS, bool GRAD, int KEEP = 0>
+// ROWS (gradient only, KEEP = 0): the lanes' own gradient rows also go to CpepArgs::lane_rows.  A kernel of its own, so that
+// the kernels every other launch runs are the ones they were (profiles/scores.txt).
+template <class Net, int NS, bool GRAD, int KEEP = 0, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP != 0 || (GRAD && Net::HAS_RW)) ? 2 : 1))) void cpep_kernel(CpepArgs a) {
     constexpr int P = Net::P;
     constexpr int NC = Net::NC;
@@ -490,10 +492,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
             double ce[NC];
             ce[0] = Net::cond_input(a.cond[set * a.set_stride_cond + ie]);
             if (active) a.g_cond[set * a.set_stride_cond + ie] = Net::grad_cond(p, acc, ce);
+            if constexpr (ROWS) store_lane_rows<Net, NC>(acc, ce, active, a.lane_rows + (set * P) * N + ie, N);
             static_assert(kWide, "the resident-layer kernel has a factor table: 35 rows of LDS");
             block_reduce_expand_wide<Net, NC>(acc, ce, active ? 1.0 : 0.0, red_loss, red_fail, smem, out, lane);
         } else {
         if (active) a.g_cond[set * a.set_stride_cond + i] = Net::grad_cond(p, acc, cst);
+        if constexpr (ROWS) store_lane_rows<Net, NC>(acc, cst, active, a.lane_rows + (set * P) * N + i, N);
         if constexpr (kWide) block_reduce_expand_wide<Net, NC>(acc, cst, active ? 1.0 : 0.0, red_loss, red_fail, smem, out, lane);
         else block_reduce_expand<Net, NC>(acc, cst, active ? 1.0 : 0.0, red_loss, red_fail, s_red, out, lane);
         }
@@ -538,6 +542,12 @@ static hipError_t launch_one(const CpepArgs& a, hipStream_t s) {
                 hipLaunchKernelGGL((cpep_kernel<Net, NS, true, 2>), dim3((unsigned)nblocks, 1), dim3(kBlock), lds, s, a);
             else
                 hipLaunchKernelGGL((cpep_kernel<Net, NS, true, 1>), dim3((unsigned)nblocks, 1), dim3(kBlock), lds, s, a);
+            return hipGetLastError();
+        }
+    }
+    if constexpr (GRAD) {
+        if (a.lane_rows != nullptr) {
+            hipLaunchKernelGGL((cpep_kernel<Net, NS, true, 0, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
             return hipGetLastError();
         }
     }

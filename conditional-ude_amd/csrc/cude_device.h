@@ -1353,6 +1353,17 @@ __device__ __forceinline__ void block_reduce_expand(const A& acc, const double (
     }
 }
 
+// The gradient while it is still one row per lane (cude_subject_scores): entry q of the lane's own network gradient goes to
+// rows[q * N], rows = the launch's table + (set * P) * N + subject ([set][P][N]: a wave's 64 stores of one q are one
+// contiguous stretch).  Called right before the reduction above by the kernels compiled with ROWS.
+template <class Net, int NCST, class A>
+__device__ __forceinline__ void store_lane_rows(const A& acc, const double (&cst)[NCST], bool active, double* rows, int64_t N) {
+    if (active) {
+#pragma unroll
+        for (int q = 0; q < Net::P; q++) rows[(int64_t)q * N] = Net::grad_elem(q, acc, cst);
+    }
+}
+
 // block_reduce_expand for a kernel that has kRedWideRows rows of LDS to spare at that point (the fixed-step c-peptide
 // gradient kernels with a layer-1 factor table: cude_cpep.hip).  Every row of a chunk is written TWICE in a row, as 128
 // entries, so lane r finds the entries (l + r) & 63, l = 0 ... 63, of its row at the constant offsets l from one base

@@ -125,6 +125,10 @@ struct CpepArgs {
 #ifdef CUDE_WAVE_TIMING
     long long* dbg;          // development builds only: [nblocks][4] = {start, end of forward, end, hw id} per wave
 #endif
+    double* lane_rows;       // gradient launches of the one-lane kernels (cude_subject_scores): [n_sets][P][N], entry q of the
+                             // network gradient of subject i in set k at ((k P + q) N + i) -- gen_acc's layout -- as the lane
+                             // holds it right before the workgroup's reduction; at the SUBJECT's index, also under perm.
+                             // nullptr = not wanted.  The fallback kernel keeps this table anyway: its gen_acc IS the table.
 };
 
 // SAEM E-step (Metropolis-Hastings)
@@ -266,6 +270,7 @@ struct SuppArgs {
     // ... of several parameter sets (cude_predictive_bands): set k writes traj + k * traj_set_stride; the launch starts at
     // workgroup blk_first of the population and covers blk_count of them (0 = the rest); 0 / 0 / 0: as ever
     int64_t traj_set_stride, blk_first, blk_count;
+    double* lane_rows;       // as CpepArgs
 };
 // workgroups of a one-lane launch: the whole population, or the stretch the argument block names
 template <class A>
@@ -550,6 +555,26 @@ hipError_t launch_marginal_accumulate(const MarginalArgs& a, int k0, int kn, con
 // outputs [N] each (null: not wanted); n_failed (one zeroed int32): subjects without a finite term
 hipError_t launch_marginal_finish(const MarginalArgs& a, double* logml, double* post_mean, double* post_var, double* post_sse,
                                   double* ess, int32_t* n_failed, hipStream_t s);
+// per-subject network scores (cude_subject_scores, cude_scores.hip; the numbered rules in include/cude.h): the running
+// state of the fold, kept in device memory between the launches of a call
+struct ScoresArgs {
+    int64_t N;
+    int32_t P;
+    double* s;                                    // [P][N] weighted rows (after the finish: NaN rows of failed subjects, masked)
+    double* wsse;                                 // [N] weighted SSE
+    int32_t* bad;                                 // [N] sets with weight whose SSE or row was not finite
+    int32_t* fail;                                // [N] 1 = failed subject (written by the finish)
+};
+// sets [k0, k0 + kn) of a call into the state, in set order: rows [kn][P][N] (CpepArgs::lane_rows), sse and w [kn][N]
+// (w null: 1); first: the state starts from zero
+hipError_t launch_scores_fold(const ScoresArgs& a, int kn, bool first, const double* rows, const double* sse, const double* w,
+                              hipStream_t s);
+// failures and the parameter mask (null: none) in place; n_failed (one zeroed int32): failed subjects; score_out_dev: the
+// table as [N][P] as well, or null
+hipError_t launch_scores_finish(const ScoresArgs& a, const double* mask, int32_t* n_failed, double* score_out_dev, hipStream_t s);
+// sum [P] and cross [P][P] over the subjects that did not fail (either null: not wanted); partial: scores_cross_partials doubles
+size_t scores_cross_partials(int64_t N, int P);
+hipError_t launch_scores_cross(const ScoresArgs& a, double* partial, double* sum, double* cross, hipStream_t s);
 // exact order statistics and the sequential mean of every (subject, output time) column of a multi-set dense-output slab
 // (cude_predictive_bands, cude_predictive.hip).  slab: value of set k, column q at slab[k * set_stride + q * col_stride];
 // columns q in [0, n_cols) with q = j + Tc * (subject - first subject of the launch), j the time inside the chunk

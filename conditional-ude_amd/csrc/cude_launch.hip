@@ -711,8 +711,11 @@ double sets_scratch_budget(cude_ctx* c) {
 //   out + k * (P + 2)          <- [masked network gradient (P); sum of SSE; failed subjects], summed over the ranks
 // (the L2 term and the loss value are the caller's: launch_finish_sets).  The set index is the grid's second dimension
 // (third on the time-split path); sets are launched in groups as large as the scratch budget allows.
+// rows (cude_subject_scores): the launches also leave every lane's own gradient row and the per-subject SSEs behind, in the
+// caller's tables.  Such a call always takes the one-lane kernels, with inv_n = 1 (a row is d SSE_i / d theta itself),
+// needs stride_cond == N, and leaves `out` this rank's own (it is the caller's scratch).
 int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t stride_nn, const double* cond,
-                         int64_t stride_cond, double* g_cond, double* out) {
+                         int64_t stride_cond, double* g_cond, double* out, const SetsRows* rows) {
     int32_t rc = CUDE_OK;
     const int P = c->P, S = c->cfg.n_steps;
     const int64_t N = c->N, nb = c->nblocks;
@@ -723,12 +726,13 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
     // short waves instead.  Same kernels as cude_loss_grad on this context, so a set's result is bit-identical to it.
     const int L = c->chunks;
     const bool split = !supp && L > 1 && c->blk0 == 0 && nb * (int64_t)std::min<int64_t>(n_sets, 64) <= 512 &&
-                       c->opt.ms_split;
+                       c->opt.ms_split && !rows;
+    if (rows && stride_cond != N) return fail(CUDE_ERR_ARG, "gradient rows need the sets' conditionals as [n_sets][N]");
     if ((rc = ensure_tape(c))) return rc;                 // (fixes the capacity the per-set tapes share)
     if ((rc = maybe_regroup(c))) return rc;
     const bool gen = c->net.generic();
     const int64_t tape_rows = tape_doubles_per_set(c) / N;
-    const double per_set = 8.0 * ((double)nb * (P + 2) + (double)tape_rows * N + (gen ? (double)P * N : 0.0) +
+    const double per_set = 8.0 * ((double)nb * (P + 2) + (double)tape_rows * N + (gen && !rows ? (double)P * N : 0.0) +
                                   (supp && !adaptive(c) ? (double)cude::supp_ckpt_rows(S, c->T) * N : 0.0) +
                                   (split ? (double)L * (3 + c->T) * N + 5.0 * S * N + (double)L * N + (double)L * nb * P : 0.0));
     // sets per launch: bounded by the grid's y / z dimension and the scratch budget
@@ -743,7 +747,14 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
     HIP_TRY(c->ms_part.reserve((size_t)chunk * nb * (P + 2)));
     if (supp && !adaptive(c) && !gen) HIP_TRY(c->ms_ckpt.reserve((size_t)chunk * cude::supp_ckpt_rows(S, c->T) * N));
     if (adaptive(c) || gen) HIP_TRY(c->ms_tape.reserve((size_t)chunk * tape_rows * N));
-    if (gen) HIP_TRY(c->ms_gacc.reserve((size_t)chunk * P * N));
+    if (gen && !rows) HIP_TRY(c->ms_gacc.reserve((size_t)chunk * P * N));
+    // (the fallback kernel's accumulators ARE the rows: they go straight into the caller's table)
+    const auto want_rows = [&](auto& a, int64_t k0) {
+        a.inv_n = 1.0;
+        a.sse = rows->sse + k0 * N;
+        a.lane_rows = rows->rows + k0 * (int64_t)P * N;
+        if (gen) a.gen_acc = a.lane_rows;
+    };
     for (int64_t k0 = 0; k0 < n_sets; k0 += chunk) {
         const int64_t kn = std::min<int64_t>(chunk, n_sets - k0);
         const double* nn_k = nn + k0 * stride_nn;
@@ -776,6 +787,7 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
             a.n_sets = (int32_t)kn; a.set_stride_nn = stride_nn; a.set_stride_cond = stride_cond;
             if (adaptive(c) || gen) a.tape = c->ms_tape.p;     // (tape_n: the counts of set 0, for the re-ordering)
             if (gen) a.gen_acc = c->ms_gacc.p;
+            if (rows) { want_rows(a, k0); a.team = -1; }
             // (several sets are several rounds: no alternating issue priority by the library's rule; an explicit "prio_shift"
             // option is honoured, so that the switch can be exercised on these launches too)
             if (!adaptive(c) && !gen && c->opt.prio_shift > 0) {
@@ -789,7 +801,8 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
             a.ckpt = c->ms_ckpt.p; a.g_cond = g_cond_k; a.partials = c->ms_part.p;
             if (adaptive(c) || gen) a.tape = c->ms_tape.p;
             if (gen) a.gen_acc = c->ms_gacc.p;
-            if (!adaptive(c) && !a.ckpt_steps_only && supp_keep_activations(c, kn)) {
+            if (rows) { want_rows(a, k0); a.ckpt_steps_only = 0; }      // (the stage-input kernel: the one compiled with rows)
+            if (!rows && !adaptive(c) && !a.ckpt_steps_only && supp_keep_activations(c, kn)) {
                 HIP_TRY(c->ms_act.reserve((size_t)kn * supp_act_doubles(c)));
                 a.act = c->ms_act.p;
             }
@@ -799,9 +812,19 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
         if (adaptive(c)) { c->have_counts = true; c->have_tape = false; }   // (step counts of the first set; its tape is ms_tape)
         if (!split)
             HIP_TRY(cude::launch_reduce_cols(c->ms_part.p, nb, P + 2, 0, P + 2, out_k, c->stream, (int)kn, c->param_mask.p, P));
-        if (distributed(c) && (rc = allreduce_dev(c, out_k, (size_t)kn * (P + 2)))) return rc;
+        if (!rows && distributed(c) && (rc = allreduce_dev(c, out_k, (size_t)kn * (P + 2)))) return rc;
     }
     return CUDE_OK;
+}
+
+// Sets per eval_sets_device call of cude_subject_scores: the rows table ([P][N] per set) and the per-set rows of
+// conditionals, weights, SSEs and conditional gradients next to the launch's own scratch (whose share of the budget
+// eval_sets_device takes by itself, so half of the budget each); option "profile_chunk" > 0 lowers it.
+int64_t scores_chunk_sets(cude_ctx* c, int64_t n_sets) {
+    const double per_set = 8.0 * ((double)c->P + 4.0) * (double)c->N;
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_sets, 32768), (int64_t)(0.5 * sets_scratch_budget(c) / per_set)));
+    if (c->opt.profile_chunk > 0) chunk = std::min<int64_t>(chunk, c->opt.profile_chunk);
+    return chunk;
 }
 
 }  // namespace api
@@ -1289,6 +1312,74 @@ int32_t cude_marginal_likelihood(cude_ctx* c, int32_t n_nodes, const double* nod
     if (n_bad_out) HIP_TRY(hipMemcpyAsync(n_bad_out, d_bad.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     int32_t failed = 0;
     HIP_TRY(hipMemcpyAsync(&failed, d_bad.p + N, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_failed = failed;
+    return CUDE_OK;
+}
+
+int32_t cude_subject_scores(cude_ctx* c, int32_t n_sets, const double* cond_sets, const double* weights, double* score_out,
+                            double* wsse_out, int32_t* bad_out, double* sum_out, double* cross_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_subject_scores under stream capture");
+    if (n_sets < 1) return fail(CUDE_ERR_ARG, "n_sets must be >= 1");
+    if (!cond_sets && n_sets > 1) return fail(CUDE_ERR_ARG, "cond_sets is NULL with n_sets > 1");
+    if (!cond_sets && !c->have_cond) return fail(CUDE_ERR_STATE, "cond_sets is NULL and the conditional parameters are not set");
+    if (!score_out && !wsse_out && !bad_out && !sum_out && !cross_out) return fail(CUDE_ERR_ARG, "no output requested");
+    const int P = c->P;
+    const int64_t N = c->N, K = n_sets;
+    if (weights)
+        for (int64_t j = 0; j < K * N; j++)
+            if (!std::isfinite(weights[j])) return fail(CUDE_ERR_ARG, "weights must be finite");
+    const int64_t chunk = scores_chunk_sets(c, K);
+    // per-set rows: conditionals, weights, SSEs, conditional gradients (scratch of the launch); state: s [P][N], wsse [N],
+    // then the caller's [N][P] table, sum [P] and cross [P][P]
+    HIP_TRY(c->sc_rows.reserve((size_t)chunk * P * N));
+    HIP_TRY(c->sc_sets.reserve((size_t)chunk * 4 * N));
+    HIP_TRY(c->sc_state.reserve((size_t)(2 * P + 1) * N + (size_t)P * (P + 1)));
+    HIP_TRY(c->sc_int.reserve((size_t)2 * N + 1));
+    HIP_TRY(c->ms_out.reserve((size_t)chunk * (P + 2)));
+    double* const d_cond = c->sc_sets.p;
+    double* const d_w = d_cond + chunk * N;
+    double* const d_sse = d_w + chunk * N;
+    double* const d_gcond = d_sse + chunk * N;
+    cude::ScoresArgs sa{};
+    sa.N = N; sa.P = P;
+    sa.s = c->sc_state.p; sa.wsse = sa.s + (size_t)P * N;
+    double* const d_table = sa.wsse + N;
+    double* const d_sum = d_table + (size_t)P * N;
+    double* const d_cross = d_sum + P;
+    sa.bad = c->sc_int.p; sa.fail = sa.bad + N;
+    int32_t* const d_nfail = sa.fail + N;
+    const SetsRows rows{c->sc_rows.p, d_sse};
+    for (int64_t k0 = 0; k0 < K; k0 += chunk) {
+        const int64_t kn = std::min<int64_t>(chunk, K - k0);
+        const double* cond_k = c->cond.p;                         // (NULL: the context's own conditionals, one set)
+        if (cond_sets) {
+            HIP_TRY(hipMemcpyAsync(d_cond, cond_sets + k0 * N, kn * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            cond_k = d_cond;
+        }
+        if (weights)
+            HIP_TRY(hipMemcpyAsync(d_w, weights + k0 * N, kn * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if ((rc = eval_sets_device(c, kn, c->nn.p, 0, cond_k, N, d_gcond, c->ms_out.p, &rows))) return rc;
+        HIP_TRY(cude::launch_scores_fold(sa, (int)kn, k0 == 0, c->sc_rows.p, d_sse, weights ? d_w : nullptr, c->stream));
+        // (the chunk buffers are the next chunk's too: copies from pageable memory are staged in stream order)
+    }
+    HIP_TRY(hipMemsetAsync(d_nfail, 0, sizeof(int32_t), c->stream));
+    HIP_TRY(cude::launch_scores_finish(sa, c->param_mask.p, d_nfail, score_out ? d_table : nullptr, c->stream));
+    if (sum_out || cross_out) {
+        HIP_TRY(c->sc_part.reserve(cude::scores_cross_partials(N, P)));
+        HIP_TRY(cude::launch_scores_cross(sa, c->sc_part.p, d_sum, d_cross, c->stream));
+    }
+    if (score_out) HIP_TRY(hipMemcpyAsync(score_out, d_table, (size_t)P * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (wsse_out) HIP_TRY(hipMemcpyAsync(wsse_out, sa.wsse, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (bad_out) HIP_TRY(hipMemcpyAsync(bad_out, sa.bad, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (sum_out) HIP_TRY(hipMemcpyAsync(sum_out, d_sum, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (cross_out) HIP_TRY(hipMemcpyAsync(cross_out, d_cross, (size_t)P * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    int32_t failed = 0;
+    HIP_TRY(hipMemcpyAsync(&failed, d_nfail, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->last_failed = failed;
     return CUDE_OK;

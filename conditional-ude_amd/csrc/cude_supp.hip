@@ -137,7 +137,9 @@ constexpr int supp_waves() {
     return (GRAD && SuppNet<W, D>::NACC <= 64) ? 2 : 1;
 #endif
 }
-template <int W, int D, bool GRAD, bool STORE, bool YONLY, int HA = kActHiddenTanh, int OA = kActOutSoftplus>
+// ROWS (gradient only, stage-input mode without kept activations): the lanes' own gradient rows also go to
+// SuppArgs::lane_rows; a kernel of its own, as cpep_kernel's
+template <int W, int D, bool GRAD, bool STORE, bool YONLY, int HA = kActHiddenTanh, int OA = kActOutSoftplus, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(supp_waves<W, D, GRAD>()))) void supp_kernel(SuppArgs a) {
     using R = SuppRhs<W, D, HA, OA>;
     using Net = typename R::Net;
@@ -459,6 +461,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(supp_wav
         __syncthreads();                   // s_red aliases s_K, which the reverse sweep has just been using
         const double cst_end[1] = {exp(a.cond[set * a.set_stride_cond + i])};      // not kept live across the sweeps
         if (active) a.g_cond[set * a.set_stride_cond + i] = Net::grad_cond(p, acc, cst_end);
+        if constexpr (ROWS) store_lane_rows<Net, 1>(acc, cst_end, active, a.lane_rows + (set * P) * N + i, N);
         block_reduce_expand<Net, 1>(acc, cst_end, active ? 1.0 : 0.0, red_loss, red_fail, s_red, out, lane);
     }
 #undef KROW
@@ -475,6 +478,13 @@ static hipError_t launch_one(const SuppArgs& a, hipStream_t s) {
                                                  (GRAD ? 6 + SuppAcc<typename SuppRhs<W, D, HA, OA>::Net>::rows : 0)) * kBlock;
     if (a.rho == nullptr || a.obs_rho == nullptr) return hipErrorInvalidValue;
     const unsigned n_sets = a.n_sets > 0 ? (unsigned)a.n_sets : 1u;
+    if constexpr (GRAD && !STORE && !YONLY) {
+        if (a.lane_rows != nullptr) {
+            hipLaunchKernelGGL((supp_kernel<W, D, true, false, false, HA, OA, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
+            return hipGetLastError();
+        }
+    }
+    if (a.lane_rows != nullptr) return hipErrorInvalidValue;      // (rows: the stage-input kernel without kept activations only)
     hipLaunchKernelGGL((supp_kernel<W, D, GRAD, STORE, YONLY, HA, OA>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a);
     return hipGetLastError();
 }

@@ -1475,6 +1475,41 @@ def grid_rule(lo, hi, n):
     return x, np.log(w)
 
 
+def _marginal_solve(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, method, n_nodes,
+                    grid_halfwidth, lower, upper, first_step, seed, n_steps, want=False, center=None, scale=None):
+    """The rule of marginal_likelihood and its device call: (population, the engine's dict, center, scale).  want: the
+    points and terms as well.  center / scale given: the rule is placed there instead of at the MAP (not for "grid")."""
+    if method not in ("quadrature", "grid", "importance"):
+        raise ValueError('method must be "quadrature", "grid" or "importance"')
+    sym = isinstance(models[0], CPeptideODEModel)
+    pop = _population(models, timepoints, cpeptide_data, n_steps, cond_space="raw" if sym else "log")
+    eng, N = pop.engine, pop.N
+    eng.set_params(pop.shared if sym and nn is None else nn, None)
+    sigma, omega, prior_mean = float(sigma), float(omega), float(prior_mean)
+    if method == "grid":
+        z, a = grid_rule(prior_mean - grid_halfwidth * omega, prior_mean + grid_halfwidth * omega, n_nodes)
+        center, scale = np.zeros(N), np.ones(N)
+        r = eng.marginal_likelihood(sigma, prior_mean, omega, nodes=z, log_weights=a, center=center, want_points=want,
+                                    want_terms=want)
+    else:
+        if center is None or scale is None:
+            pw = (sigma / omega) ** 2
+            start = None if betas is None else np.asarray(betas, dtype=np.float64).reshape(-1)[:N]
+            center, _, _, info = _fit_box(eng, lower, upper, 81 if start is None else 0, 48, "newton", start=start,
+                                          penalty_weight=pw, penalty_center=prior_mean)
+            scale = sigma / np.sqrt(info + pw)
+        if method == "quadrature":
+            z, a = gauss_hermite_rule(n_nodes)
+            r = eng.marginal_likelihood(sigma, prior_mean, omega, nodes=z, log_weights=a, center=center, scale=scale,
+                                        want_points=want, want_terms=want)
+        else:
+            if seed is not None:
+                eng.set_rng(seed)
+            r = eng.marginal_likelihood(sigma, prior_mean, omega, n_draws=n_nodes, first_step=first_step, center=center,
+                                        scale=scale, want_points=want, want_terms=want)
+    return pop, r, center, scale
+
+
 def marginal_likelihood(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, method="quadrature",
                         n_nodes=33, grid_halfwidth=8.0, lower=-6.0, upper=4.0, first_step=0, seed=None, normalized=False,
                         n_steps=None):
@@ -1488,35 +1523,157 @@ def marginal_likelihood(betas, nn, models, timepoints, cpeptide_data, sigma, pri
     Returns a namespace: logml, post_mean, post_var, post_sse, ess (N,), n_bad (N,) int32, center, scale (N,), and total =
     the sum of logml in subject order.  The likelihood follows the reference's convention (no 2 pi constant);
     normalized = True adds -(T/2) log(2 pi) per subject."""
-    if method not in ("quadrature", "grid", "importance"):
-        raise ValueError('method must be "quadrature", "grid" or "importance"')
-    sym = isinstance(models[0], CPeptideODEModel)
-    pop = _population(models, timepoints, cpeptide_data, n_steps, cond_space="raw" if sym else "log")
-    eng, N = pop.engine, pop.N
-    eng.set_params(pop.shared if sym and nn is None else nn, None)
-    sigma, omega, prior_mean = float(sigma), float(omega), float(prior_mean)
-    if method == "grid":
-        z, a = grid_rule(prior_mean - grid_halfwidth * omega, prior_mean + grid_halfwidth * omega, n_nodes)
-        center, scale = np.zeros(N), np.ones(N)
-        r = eng.marginal_likelihood(sigma, prior_mean, omega, nodes=z, log_weights=a, center=center)
-    else:
-        pw = (sigma / omega) ** 2
-        start = None if betas is None else np.asarray(betas, dtype=np.float64).reshape(-1)[:N]
-        center, _, _, info = _fit_box(eng, lower, upper, 81 if start is None else 0, 48, "newton", start=start,
-                                      penalty_weight=pw, penalty_center=prior_mean)
-        scale = sigma / np.sqrt(info + pw)
-        if method == "quadrature":
-            z, a = gauss_hermite_rule(n_nodes)
-            r = eng.marginal_likelihood(sigma, prior_mean, omega, nodes=z, log_weights=a, center=center, scale=scale)
-        else:
-            if seed is not None:
-                eng.set_rng(seed)
-            r = eng.marginal_likelihood(sigma, prior_mean, omega, n_draws=n_nodes, first_step=first_step, center=center,
-                                        scale=scale)
+    pop, r, center, scale = _marginal_solve(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega,
+                                            method=method, n_nodes=n_nodes, grid_halfwidth=grid_halfwidth, lower=lower,
+                                            upper=upper, first_step=first_step, seed=seed, n_steps=n_steps)
     logml = r["logml"] - 0.5 * pop.T * math.log(2.0 * math.pi) if normalized else r["logml"]
     return SimpleNamespace(logml=logml, total=float(np.add.accumulate(logml)[-1]), post_mean=r["post_mean"],
                            post_var=r["post_var"], post_sse=r["post_sse"], ess=r["ess"], n_bad=r["n_bad"], center=center,
                            scale=scale)
+
+
+def posterior_weights(terms, logml, scale=None):
+    """Posterior weights of a rule's nodes from cude_marginal_likelihood's terms (K, N) and logml (N,): w_ik = exp(t_ik -
+    (logml_i - log scale_i)); they sum to 1 over k for every subject with a finite logml.  A bad node has t = -Inf and gets
+    w = 0 exactly (so does every node of a subject without a finite term)."""
+    t = np.asarray(terms, dtype=np.float64)
+    lse = np.asarray(logml, dtype=np.float64) - (0.0 if scale is None else np.log(np.asarray(scale, dtype=np.float64)))
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.exp(t - lse[None, :])
+    return np.where(np.isneginf(t), 0.0, w)
+
+
+def subject_scores(theta, args, *, n_steps=None):
+    """The (N, P) table of per-subject scores d SSE_i / d theta.neural at the fitted conditionals theta.conditional
+    (cude_subject_scores with one set and no weights); args = (models, timepoints, cpeptide_data) as `loss`.  Rows of
+    failed subjects are NaN.  These rows hold the conditionals fixed: an information matrix built from them ignores the
+    uncertainty of the conditionals (network_standard_errors uses the marginal scores instead)."""
+    models, timepoints, data = args
+    if _is_model(models):
+        models, data = [models], np.asarray(data)[None, :]
+    if isinstance(models[0], CPeptideODEModel):
+        pop = _population(models, timepoints, data, n_steps, cond_space="raw")
+        nn = getattr(theta, "neural", None)
+        cond = getattr(theta, "conditional", getattr(theta, "ode", theta))
+        pop.engine.set_params(pop.shared if nn is None else nn, np.asarray(cond, dtype=np.float64).reshape(-1)[:pop.N])
+    else:
+        pop = _population(models, timepoints, data, n_steps)
+        pop.engine.set_params(theta.neural, np.asarray(theta.conditional, dtype=np.float64).reshape(-1)[:pop.N])
+    return pop.engine.subject_scores(want=("scores",))["scores"]
+
+
+def marginal_score(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, method="quadrature",
+                   n_nodes=33, grid_halfwidth=8.0, lower=-6.0, upper=4.0, first_step=0, seed=None, normalized=False,
+                   n_steps=None, center=None, scale=None):
+    """Value and network gradient of the marginal log-likelihood that marginal_likelihood (same arguments) computes, by
+    Fisher's identity: the rule is run with its points and terms kept, the posterior weights of the nodes w_ik =
+    exp(t_ik - (logml_i - log scale_i)) are formed on the host (a bad node has t = -Inf, so w = 0), and
+    cude_subject_scores folds the per-node gradient rows with them: s_i = sum_k w_ik d SSE_i(x_ik) / d theta.
+    Returns a namespace: logml (N,), total, scores = -s_i / (2 sigma^2) (N, P) -- every subject's own gradient of logml_i
+    --, gradient = -sum_i s_i / (2 sigma^2) (P,), opg = sum_i s_i s_i^T / (4 sigma^4) (P, P), wsse (N,) = the posterior
+    expectation of the SSE, n_failed, center, scale.
+    This is the derivative of the RULE's value with its points and weights held fixed.  With points re-centred at a MAP
+    that itself depends on the network ("quadrature", "importance") it omits the dependence of the nodes on the network;
+    that dependence is of the order of the rule's own quadrature error (it vanishes for the exact integral), and it is
+    absent for method = "grid", whose nodes do not move.  The K x N weights cross to the host and back once, and the
+    forward half of every node's solve runs twice: once for the weights, once under the adjoint."""
+    pop, r, center, scale = _marginal_solve(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega,
+                                            method=method, n_nodes=n_nodes, grid_halfwidth=grid_halfwidth, lower=lower,
+                                            upper=upper, first_step=first_step, seed=seed, n_steps=n_steps, want=True,
+                                            center=center, scale=scale)
+    w = posterior_weights(r["terms"], r["logml"], scale)
+    s = pop.engine.subject_scores(r["points"], w)
+    n_failed = pop.engine.n_failed()
+    c = 1.0 / (2.0 * float(sigma) ** 2)
+    logml = r["logml"] - 0.5 * pop.T * math.log(2.0 * math.pi) if normalized else r["logml"]
+    return SimpleNamespace(logml=logml, total=float(np.add.accumulate(logml)[-1]), scores=-c * s["scores"],
+                           gradient=-c * s["sum"], opg=(c * c) * s["cross"], wsse=s["wsse"], n_failed=n_failed,
+                           center=center, scale=scale, post_mean=r["post_mean"], post_var=r["post_var"],
+                           post_sse=r["post_sse"])
+
+
+def opg_covariance(opg):
+    """(cov, se) from an outer-product-of-gradients information matrix: cov = pinv(opg) (the matrix has rank at most the
+    number of subjects, and less with frozen parameters, whose rows and columns are zero), se = sqrt(diag(cov))."""
+    m = np.asarray(opg, dtype=np.float64)
+    cov = np.linalg.pinv(0.5 * (m + m.T), hermitian=True)
+    return cov, np.sqrt(np.clip(np.diag(cov), 0.0, None))
+
+
+def network_standard_errors(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, **kwargs):
+    """Standard errors of the network parameters from the cross-product (OPG, "S matrix") estimator of the information:
+    opg = sum_i g_i g_i^T with g_i = subject i's gradient of its MARGINAL log-likelihood (marginal_score, same arguments),
+    cov = pinv(opg), se = sqrt(diag(cov)).  Returns a namespace: cov (P, P), se (P,), opg, rank, gradient, total.
+    The rank of opg is at most N, the number of subjects: with fewer subjects than parameters the pseudo-inverse covers
+    the span of the scores only, and se is 0 outside it (rank tells).  Scores taken at fitted conditionals instead
+    (subject_scores: the K = 1 table) would ignore the uncertainty of the conditionals and understate these errors; this
+    function does not use them."""
+    ms = marginal_score(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, **kwargs)
+    cov, se = opg_covariance(ms.opg)
+    return SimpleNamespace(cov=cov, se=se, opg=ms.opg, rank=int(np.linalg.matrix_rank(ms.opg, hermitian=True)),
+                           gradient=ms.gradient, total=ms.total)
+
+
+def _marginal_em_rounds(x0, hyper0, objective, update, rounds, iterations):
+    """The loop of train_marginal on any objective: per round L-BFGS (at most `iterations` accepted iterations) on
+    x -> objective(x, hyper) = (-total, -gradient, moments), then hyper = update(moments of the round's last accepted
+    point).  Returns (x, hyper, trace, starts): trace holds `total` at the start of every round and after every accepted
+    iteration, starts the positions in it at which the rounds begin."""
+    x, hyper, trace, starts = np.array(x0, dtype=np.float64), hyper0, [], []
+    for _ in range(int(rounds)):
+        seen = {}
+        starts.append(len(trace))
+
+        def fg(p, hyper=hyper, seen=seen):
+            f, g, moments = objective(p, hyper)
+            seen[p.tobytes()] = moments
+            return f, g
+
+        f0, _ = fg(x)
+        trace.append(-float(f0))
+        if not np.isfinite(f0):
+            break
+        res = lbfgs(fg, x, maxiters=int(iterations), callback=lambda p, f: trace.append(-float(f)) or False)
+        x = res["x"]
+        moments = seen.get(x.tobytes())
+        if moments is None:
+            moments = objective(x, hyper)[2]
+        hyper = update(moments)
+    return x, hyper, trace, starts
+
+
+def train_marginal(nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, rounds=1, iterations=5,
+                   method="grid", n_nodes=33, grid_halfwidth=8.0, n_steps=None, **kwargs):
+    """Direct maximum-marginal-likelihood training of the network (quadrature EM): per round, L-BFGS on -total over the
+    network parameters with marginal_score as value and gradient -- the rule's nodes fixed for the round (method = "grid":
+    they never move; otherwise the MAP centres of the round's first point are kept) -- then the closed-form EM updates
+    (em_updates) of (sigma^2, prior_mean, omega^2) from the posterior moments at the round's last point.  Returns a
+    namespace: nn, sigma, prior_mean, omega, trace = `total` at the start of every round and after every accepted L-BFGS
+    iteration (inside a round it never decreases: the line search only accepts a decrease of -total), round_starts = where
+    in the trace the rounds begin."""
+    T = len(timepoints)
+    state = {"center": None, "scale": None}
+
+    def objective(p, hyper):
+        s, m, o = hyper
+        ms = marginal_score(None, p, models, timepoints, cpeptide_data, s, m, o, method=method, n_nodes=n_nodes,
+                            grid_halfwidth=grid_halfwidth, n_steps=n_steps, center=state["center"], scale=state["scale"],
+                            **kwargs)
+        if method != "grid" and state["center"] is None:
+            state["center"], state["scale"] = ms.center, ms.scale
+        if ms.n_failed > 0 or not np.isfinite(ms.total):
+            return np.inf, np.zeros_like(p), None
+        return -ms.total, -ms.gradient, (ms.post_mean, ms.post_var, ms.wsse)
+
+    def update(moments):
+        state["center"] = state["scale"] = None
+        s2, mu, o2 = em_updates(*moments, T)
+        return math.sqrt(s2), mu, math.sqrt(o2)
+
+    x, hyper, trace, starts = _marginal_em_rounds(np.asarray(nn, dtype=np.float64).reshape(-1),
+                                                  (float(sigma), float(prior_mean), float(omega)), objective, update, rounds,
+                                                  iterations)
+    return SimpleNamespace(nn=x, sigma=hyper[0], prior_mean=hyper[1], omega=hyper[2], trace=trace, round_starts=starts)
 
 
 def information_criteria(total_logml, n_params, n_subjects, n_obs):

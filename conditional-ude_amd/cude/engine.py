@@ -463,6 +463,33 @@ class Engine:
             _ptr(out["ess"]), _ptr(out["n_bad"]), _ptr(out["points"]), _ptr(out["terms"])))
         return out
 
+    def subject_scores(self, cond_sets=None, weights=None, want=("scores", "wsse", "bad", "sum", "cross")):
+        """Per-subject scores of the shared parameters on the device (cude_subject_scores): s_i = sum_k w_ik d SSE_i(x_ik) /
+        d theta in set order, with cond_sets (K, N) -- None: the context's conditional parameters, one set -- and weights
+        (K, N) -- None: 1; a set with weight 0 is skipped for that subject.  Returns dict(scores (N, P), wsse (N,), bad
+        (N,) int32 = sets with weight whose SSE or row was not finite, sum (P,), cross (P, P)), None for what `want`
+        leaves out.  A failed subject (bad > 0) has a NaN row and wsse, is left out of sum and cross, and is counted by
+        n_failed() afterwards."""
+        cd = None if cond_sets is None else _f64(cond_sets)
+        w = None if weights is None else _f64(weights)
+        if cd is not None and (cd.ndim != 2 or cd.shape[1] != self.N):
+            raise ValueError(f"expected cond_sets (K, {self.N})")
+        K = cd.shape[0] if cd is not None else (w.shape[0] if w is not None and w.ndim == 2 else 1)
+        if w is not None and w.shape != (K, self.N):
+            raise ValueError(f"expected weights ({K}, {self.N})")
+        unknown = set(want) - {"scores", "wsse", "bad", "sum", "cross"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        P = self.P
+        out = {"scores": np.empty((self.N, P)) if "scores" in want else None,
+               "wsse": np.empty(self.N) if "wsse" in want else None,
+               "bad": np.empty(self.N, dtype=np.int32) if "bad" in want else None,
+               "sum": np.empty(P) if "sum" in want else None,
+               "cross": np.empty((P, P)) if "cross" in want else None}
+        check(self._lib.cude_subject_scores(self._h, K, _ptr(cd), _ptr(w), _ptr(out["scores"]), _ptr(out["wsse"]),
+                                            _ptr(out["bad"]), _ptr(out["sum"]), _ptr(out["cross"])))
+        return out
+
     def fit_conditional(self, lower, upper, n_grid=41, n_iters=48, penalty_weight=0.0, penalty_center=0.0):
         """All subjects' 1-D fits of the conditional parameter with the shared parameters frozen, on the device:
         argmin_x SSE_i(x) + penalty_weight (x - penalty_center)^2 over [lower, upper] -> (x[N], objective[N], sse[N])."""

@@ -30,7 +30,7 @@ export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEMod
        profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
-       marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates
+       marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores
 
 const LIB = get(ENV, "CUDE_HIP_LIB", "libcude_hip.so")
 const MODEL_CPEP, MODEL_SUPP, MODEL_CPEP_SYM = Int32(0), Int32(1), Int32(2)
@@ -328,6 +328,23 @@ function marginal_likelihood(c::Ctx, σ, prior_η, Ω; nodes = nothing, log_weig
         cen === nothing ? C_NULL : pointer(cen), scl === nothing ? C_NULL : pointer(scl), Float64(σ), Float64(prior_η),
         Float64(Ω), logml, pmean, pvar, psse, ess, n_bad, points, terms))
     logml, pmean, pvar, psse, ess, n_bad, points, terms
+end
+
+# per-subject scores of the shared parameters on the device (cude_subject_scores): sᵢ = Σₖ wᵢₖ ∂SSEᵢ(xᵢₖ)/∂θ in set order,
+# cond_sets and weights N×K matrices (= [K][N] row-major; cond_sets = nothing: the context's conditional parameters, one
+# set; weights = nothing: 1).  Returns (scores P×N, wsse, bad, sum, cross P×P): a failed subject has a NaN column and is
+# left out of sum and cross
+function subject_scores(c::Ctx; cond_sets = nothing, weights = nothing)
+    x = cond_sets === nothing ? nothing : Matrix{Float64}(reshape(cond_sets, c.N, :))
+    w = weights === nothing ? nothing : Matrix{Float64}(reshape(weights, c.N, :))
+    K = x === nothing ? (w === nothing ? 1 : size(w, 2)) : size(x, 2)
+    (w === nothing || size(w, 2) == K) || error("subject_scores: weights and cond_sets differ in the number of sets")
+    scores = Matrix{Float64}(undef, c.P, c.N); wsse = Vector{Float64}(undef, c.N); bad = Vector{Int32}(undef, c.N)
+    total = Vector{Float64}(undef, c.P); cross = Matrix{Float64}(undef, c.P, c.P)
+    GC.@preserve x w scores wsse bad total cross check(ccall((:cude_subject_scores, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+        c.h, Int32(K), x === nothing ? C_NULL : pointer(x), w === nothing ? C_NULL : pointer(w), scores, wsse, bad, total, cross))
+    scores, wsse, bad, total, cross
 end
 
 adam_init!(c::Ctx, η; β1 = 0.9, β2 = 0.999, ϵ = 1e-8) =

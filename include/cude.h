@@ -479,6 +479,47 @@ int32_t cude_marginal_likelihood(cude_ctx* ctx, int32_t n_nodes, const double* n
                                  double* post_var_out, double* post_sse_out, double* ess_out, int32_t* n_bad_out,
                                  double* points_out, double* terms_out);
 
+/* Per-subject scores with respect to the shared (network) parameters: the weighted gradient rows
+ *   s_i = sum_k w_ik d SSE_i(x_ik) / d theta                                                              [P] per subject
+ * that every other gradient call sums over the subjects before anyone sees them, their sum, and their cross product
+ * sum_i s_i s_i^T (the outer-product-of-gradients information matrix; the "S matrix" of the pharmacometric tools).  With the
+ * posterior weights of cude_marginal_likelihood's nodes, -sum_i s_i / (2 sigma^2) is the network gradient of the marginal
+ * log-likelihood (Fisher's identity); with 0/1 or bootstrap weights it is a per-subject weighting of the shared gradient.
+ *   1. Sets: set k is the context's shared parameters with the conditional vector cond_sets[k] ([n_sets][N] row-major);
+ *      cond_sets NULL with n_sets == 1 = the context's conditional parameters.  A set is solved as
+ *      cude_multistart_loss_grad solves one -- the fixed-step map, or the accepted steps of the adaptive solve taken as
+ *      fixed arithmetic -- always on the one-lane kernels, and row_ik = d SSE_i(x_ik) / d theta is the lane's own gradient
+ *      right before those kernels add the lanes up: no 1/N, no L2 term.
+ *   2. Weights: weights [n_sets][N] row-major, finite; NULL = 1.  s_i = s_i + (w_ik row_ik) in set order k = 0 ... n_sets - 1
+ *      from 0, the product rounded, then the sum (no fma contraction); wsse_i = sum_k w_ik SSE_i(x_ik) by the same rule.  A
+ *      set with w_ik == 0 is skipped for subject i, whatever its solve gave: a bad quadrature node without posterior weight
+ *      poisons nothing.  The state lives in device memory between the launches (sets per launch: the scratch budget, and
+ *      option "profile_chunk"), and a subject's sets are folded in strictly in order by one lane: every output is
+ *      bit-identical for every chunking.
+ *   3. Failed subjects: a set with w_ik != 0 whose SSE or row is not finite makes subject i failed (so does a weighted sum
+ *      that overflows).  bad_out[i] counts such sets.  A failed subject gets NaN in its score row and wsse, is left out of
+ *      sum and cross, and is counted by cude_n_failed afterwards.  Other subjects are unaffected, bit for bit.
+ *   4. Parameter mask (cude_set_param_mask): every row is multiplied by it; a masked entry is exactly 0.0 in score_out (a
+ *      failed subject's row included), sum_out and cross_out.
+ *   5. Sum and cross product over the subjects that did not fail: sum[q] = sum_i s_i[q], cross[q][r] = sum_i s_i[q] s_i[r].
+ *      Both triangles of cross are written and equal bit for bit.  The order of the additions is fixed by N alone (blocks of
+ *      1024 subjects in index order, the blocks in order) and the same from run to run.  They are formed on the device from
+ *      the table there: the host never needs score_out to get them.  Sharded population: they are this rank's sums; the
+ *      caller adds the ranks up (cude_comm_allreduce_host).
+ *   6. Both network models, the symbolic model (P = 1) in either cond_space, fixed-step and adaptive mode, every tuned
+ *      shape with any of its activation functions, and the fallback kernel.
+ *   7. Leaves the context's parameters untouched.  Adaptive mode: cude_adaptive_steps refuses afterwards; a population of
+ *      8192 subjects or more may be regrouped as by any multi-set gradient call (cude_adaptive_regroup), on which no
+ *      per-subject result depends.
+ *   8. CUDE_ERR_ARG: n_sets < 1, cond_sets == NULL with n_sets > 1, a non-finite weight, no output requested.
+ *      CUDE_ERR_STATE: no population or shared parameters, cond_sets == NULL without conditional parameters, stream capture.
+ *   9. Everything is queued on the context's stream; one synchronisation at the end.
+ * Outputs: score_out [N][P] row-major, wsse_out [N], bad_out [N], sum_out [P], cross_out [P][P]; all optional, at least one.
+ * Not built: the terms of cude_marginal_likelihood are not handed over on the device (the caller forms the n_sets x N
+ * weights from terms_out and passes them back in), and the forward half of every set's solve runs again under the adjoint. */
+int32_t cude_subject_scores(cude_ctx* ctx, int32_t n_sets, const double* cond_sets, const double* weights,
+                            double* score_out, double* wsse_out, int32_t* bad_out, double* sum_out, double* cross_out);
+
 /* SAEM E-step on the device: n_mc Metropolis-Hastings steps of every subject's conditional parameter
  * (`mcmc_step` src/saem.jl:86-108, applied n_mcmc_steps times with the stochastic-approximation update of the
  * chain state :177-186).  The chain state is the context's conditional parameters (updated in place); the
