@@ -48,6 +48,15 @@ TEAM_SHAPES = CPEP_SHAPES[:8]                           # CUDE_CPEP_SHAPES_0
 SUPP_UNROLLED = [(3, 5), (3, 3), (3, 4), (3, 2)]        # csrc/cude_adaptive.h CUDE_SUPP_AD_UNROLLED
 TWO_WORKGROUPS = [(2, 4, 2), (3, 6, 2), (2, 5, 1)]      # first shape of each group: run with 70 subjects (a second
                                                         # workgroup, a wave of six lanes), the others with 16
+SUPP_TWO_WORKGROUPS = [(3, 5), (4, 3), (3, 1)]          # the same for the tangent and fit kernels of the suppression model
+                                                        # (tests/test_gpu_tangent_shapes.py): 70 subjects, the others 12
+# csrc/cude_device.h CUDE_CPEP_GENERAL_SHAPES / CUDE_SUPP_GENERAL_SHAPES: the shapes that are also compiled with the
+# activation pairs of CUDE_GENERAL_ACTS, here as (hidden, output) names in its order (csrc/cude_kernels.h kActHidden* /
+# kActOut*: hidden 0 tanh, 1 relu, 2 sigmoid; output 0 softplus, 1 identity)
+CPEP_GENERAL_SHAPES = [(2, 4, 2), (2, 6, 2), (3, 4, 2)]
+SUPP_GENERAL_SHAPES = [(3, 5), (3, 3)]
+GENERAL_ACTS = [("tanh", "identity"), ("relu", "softplus"), ("relu", "identity"), ("sigmoid", "softplus"),
+                ("sigmoid", "identity")]
 
 TP5 = [0.0, 30.0, 60.0, 90.0, 120.0]
 TP6 = [0.0, 15.0, 30.0, 60.0, 90.0, 120.0]
@@ -55,6 +64,10 @@ TP6 = [0.0, 15.0, 30.0, 60.0, 90.0, 120.0]
 
 def cpep_subjects(arch):
     return 70 if tuple(arch) in TWO_WORKGROUPS else 16
+
+
+def supp_subjects(shape):
+    return 70 if tuple(shape) in SUPP_TWO_WORKGROUPS else 12
 
 
 def layer_blocks(arch):
@@ -177,3 +190,65 @@ def block_ratios(g, arch):
     """{block: max-norm of the block of g / max-norm of g} over layer_blocks: each layer's weights and its biases."""
     top = np.max(np.abs(g))
     return {name: float(np.max(np.abs(g[s])) / top) for name, s in layer_blocks(arch)}
+
+
+# ----------------------------------------------------------------------------- the tangent and fit kernels' cases
+# (tests/test_gpu_tangent_shapes.py on the device, tests/test_tangent_cases_host.py for the inputs themselves)
+CPEP_BOX, SUPP_BOX = (-4.0, 3.0), (-6.0, 4.0)           # the boxes of tests/test_gpu_refine.py
+FIT_PERTURBATION = 1e-9                                 # the error the tangent kernels are allowed (GRAD_RTOL)
+
+
+def tangent_case(model, k):
+    """The fixed-step case of shape k of CPEP_SHAPES (model "cpep": five knots, 70 / 16 subjects) or SUPP_SHAPES ("supp":
+    70 / 12 subjects) -> (case, name of its conditional parameter, box of its fits)."""
+    if model == "cpep":
+        arch = CPEP_SHAPES[k]
+        return cpep_case(arch, k, TP5, cpep_subjects(arch)), "beta", CPEP_BOX
+    shape = SUPP_SHAPES[k]
+    return supp_case(shape, k, supp_subjects(shape)), "theta", SUPP_BOX
+
+
+_FIT_STUDIES = {}
+
+
+def fit_study(model, k, n_steps=30):
+    """The perturbation rule of tests/test_gpu_refine.py / test_refine_host.py on tangent_case(model, k): the restatement
+    tests/refine_ref.py from x0 = the case's conditional parameters (max_step 0.5, xtol 1e-7, 40 evaluations), and again
+    with every info and score multiplied by 1 +- 1e-9 in the four sign combinations.  The five runs are ONE call of the
+    restatement on the population repeated five times (no quantity crosses subjects; the suppression loss's weights are
+    those of the population itself).  Returns dict(case, x0, box, ref = the unperturbed run's dict(x, objective, sse,
+    info, evals, status), admissible (N,) bool: neither status nor evals changes in any of the four); computed once per
+    shape."""
+    if (model, k) in _FIT_STUDIES:
+        return _FIT_STUDIES[model, k]
+    import refine_ref as rr
+    import sensitivity_ref as ref
+    c, cond, box = tangent_case(model, k)
+    x0, arch, nn = c[cond], c["arch"], c["nn"]
+    N, f = x0.size, FIT_PERTURBATION
+    combos = [(1.0, 1.0), (1 + f, 1 + f), (1 + f, 1 / (1 + f)), (1 - f, 1 - f), (1 - f, 1 / (1 - f))]     # (info, score)
+    R = len(combos)
+    f_info, f_score = (np.repeat([q[j] for q in combos], N) for j in (0, 1))
+    if model == "cpep":
+        pop = o.CPepPopulation(c["tp"], np.tile(c["G"], (R, 1)), np.tile(c["obs"], (R, 1)), np.tile(c["age"], R),
+                               np.tile(c["t2dm"], R), covariate=(arch[0] == 3))
+
+        def ev(x):
+            with np.errstate(all="ignore"):
+                _, info, score, sse = ref.cpep_sens(nn, x, pop, arch, n_steps, 2)
+            return info * f_info, score * f_score, sse
+    else:
+        data, w2 = np.tile(c["data"], (1, 1, R)), 1.0 / o.supp_scale(c["data"]) ** 2
+
+        def ev(x):
+            with np.errstate(all="ignore"):
+                u = ref._stack(o.supp_forward(np, nn, np.asarray(x, dtype=np.complex128) + 1j * ref.H, data, c["tp"], arch,
+                                              n_steps), R * N)
+                info, score, sse = ref._summaries(u, data, w2)
+            return info * f_info, score * f_score, sse
+    r = rr.refine(ev, np.tile(x0, R), *box, max_evals=40, xtol=1e-7, max_step=0.5)
+    runs = {key: v.reshape(R, N) for key, v in r.items()}
+    admissible = np.all((runs["status"] == runs["status"][0]) & (runs["evals"] == runs["evals"][0]), axis=0)
+    out = dict(case=c, x0=x0, box=box, ref={key: v[0].copy() for key, v in runs.items()}, admissible=admissible)
+    _FIT_STUDIES[model, k] = out
+    return out

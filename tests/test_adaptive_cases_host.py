@@ -36,6 +36,26 @@ def test_shape_lists_restate_the_headers():
     assert len(ac.TP5) == 5 and len(ac.TP6) == 6
 
 
+def test_general_lists_restate_the_headers():
+    """The lists tests/test_gpu_tangent_shapes.py walks for the other activation functions, and its 70-subject cases."""
+    assert ac.CPEP_GENERAL_SHAPES == _macro("cude_device.h", "CUDE_CPEP_GENERAL_SHAPES")
+    assert ac.SUPP_GENERAL_SHAPES == _macro("cude_device.h", "CUDE_SUPP_GENERAL_SHAPES")
+    assert set(ac.CPEP_GENERAL_SHAPES) <= set(ac.CPEP_SHAPES) and set(ac.SUPP_GENERAL_SHAPES) <= set(ac.SUPP_SHAPES)
+    with open(os.path.join(CSRC, "cude_device.h")) as f:
+        pairs = re.search(r"^#define CUDE_GENERAL_ACTS\(Y\)(.*)$", f.read(), re.M).group(1)
+    pairs = [tuple(int(v) for v in t.split(",")) for t in re.findall(r"Y\(([0-9, ]+)\)", pairs)]
+    with open(os.path.join(CSRC, "cude_kernels.h")) as f:
+        text = f.read()
+    code = {name: int(v) for name, v in re.findall(r"kAct(Hidden\w+|Out\w+) = (\d+)", text)}
+    hidden = {code["HiddenTanh"]: "tanh", code["HiddenRelu"]: "relu", code["HiddenSigmoid"]: "sigmoid"}
+    output = {code["OutSoftplus"]: "softplus", code["OutIdentity"]: "identity"}
+    assert ac.GENERAL_ACTS == [(hidden[h], output[q]) for h, q in pairs] and len(pairs) == 5
+    assert ("tanh", "softplus") not in ac.GENERAL_ACTS               # the specialised default is not a general pair
+    assert all(a[0] in o.HIDDEN_ACTS and a[1] in o.OUTPUT_ACTS for a in ac.GENERAL_ACTS)
+    assert [ac.supp_subjects(s) for s in ac.SUPP_SHAPES] == [70 if s in [(3, 5), (4, 3), (3, 1)] else 12 for s in ac.SUPP_SHAPES]
+    assert [ac.cpep_subjects(a) for a in ac.CPEP_SHAPES] == [70 if a in ac.TWO_WORKGROUPS else 16 for a in ac.CPEP_SHAPES]
+
+
 @pytest.mark.parametrize("arch", [(2, 4, 2), (3, 6, 2), (2, 8, 3), (4, 3, 5), (4, 8, 1)])
 def test_biased_params(arch):
     nn, plain = ac.biased_params(arch, 5), o.glorot_params(arch, 5)
