@@ -112,6 +112,11 @@ struct CpepAd {
         ob[0] = 2.0 * (o[0] - a.obs[(int64_t)oi * a.N + i]);
         ob[1] = 0.0;
     }
+    // ... replaced by the unit seed of set `set` (kernels compiled with ROWS, Args::unit_seed > 0)
+    __device__ __forceinline__ void unit_bar(const Args& a, int oi, int64_t set, double (&ob)[NS]) const {
+        ob[0] = unit_seed_cpep(a, set, oi);
+        ob[1] = 0.0;
+    }
     // acc += wgt * d production(te) / d params  (the baseline term is collected by the caller)
     template <class A>
     __device__ __forceinline__ void vjp_net(double te, double wgt, A& acc) const {
@@ -184,6 +189,11 @@ struct SuppAd {
         ob[0] = 0.0;
 #pragma unroll
         for (int s = 1; s < 3; s++) ob[s] = 2.0 * a.iscale2[s] * (o[s] - a.data[((int64_t)s * a.T + oi) * a.N + i]);
+    }
+    __device__ __forceinline__ void unit_bar(const Args& a, int oi, int64_t set, double (&ob)[NS]) const {
+        ob[0] = 0.0;
+#pragma unroll
+        for (int s = 1; s < 3; s++) ob[s] = unit_seed_supp(a, set, oi, s);
     }
     template <class A>
     __device__ __forceinline__ void vjp(double, const double (&u)[NS], const double (&kb)[NS], double (&ub)[NS], A& acc,

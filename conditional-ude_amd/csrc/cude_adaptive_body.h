@@ -317,6 +317,7 @@ void adaptive_kernel(typename M::Args a) {
                         for (int s = 0; s < NS; s++) o[s] = 0.0;
                         o[0] = OUTV(oi);
                         m.residual_bar(a, oi, i, o, ob);
+                        if constexpr (ROWS) { if (unit_seeded<ROWS>(a)) m.unit_bar(a, oi, set, ob); }
 #pragma unroll
                         for (int s = 0; s < NS; s++) { ob[s] *= gs; yb[s] += ob[s]; ob[s] *= h; }
 #pragma unroll 1
@@ -431,6 +432,7 @@ void adaptive_kernel(typename M::Args a) {
 #pragma unroll
                     for (int s = 0; s < NS; s++) o[s] = fma(h, o[s], y[s]);
                     m.residual_bar(a, oi, i, o, ob);
+                    if constexpr (ROWS) { if (unit_seeded<ROWS>(a)) m.unit_bar(a, oi, set, ob); }
 #pragma unroll
                     for (int s = A0; s < NS; s++) { ob[s] *= gs; yb[s] += ob[s]; ob[s] *= h; }
 #pragma unroll 1

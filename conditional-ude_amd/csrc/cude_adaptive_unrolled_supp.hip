@@ -164,6 +164,7 @@ void adaptive_unrolled_supp_kernel(SuppArgs a) {
                     if (GRAD) {
                         double ob[NS];
                         m.residual_bar(a, nxt, i, o, ob);
+                        if constexpr (ROWS) { if (unit_seeded<ROWS>(a)) m.unit_bar(a, nxt, set, ob); }
                         SEED(nxt, 0) = ob[1];
                         SEED(nxt, 1) = ob[2];
                     }

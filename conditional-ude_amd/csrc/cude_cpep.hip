@@ -258,6 +258,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
             const double r = a.obs != nullptr ? o1 - a.obs[(int64_t)oi * N + i] : 0.0;   // null: cude_simulate
             sse = fma(r, r, sse);
             if (GRAD) s_res[oi * kBlock + lane] = r;
+            // (unit adjoint seed, CpepArgs::unit_seed: the reverse sweep reads 1.0 / 0.0 where it read the residual)
+            if constexpr (ROWS) { if (a.unit_seed > 0) s_res[oi * kBlock + lane] = unit_seed_cpep(a, set, oi); }
             if (a.traj != nullptr && active) {
                 double* tr = a.traj + (int64_t)NS * (oi + (int64_t)T * i);
                 tr[0] = o1;
@@ -336,7 +338,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
                 kb[6][1] = kap2;
                 double yb1 = 0.0, yb2 = 0.0;
                 while (oi >= 0 && obs_step[oi] == n) {
-                    const double g = gscale * s_res[oi * kBlock + lane];
+                    double g = gscale * s_res[oi * kBlock + lane];
+                    if constexpr (ROWS) { if (a.unit_seed > 0) g = s_res[oi * kBlock + lane]; }     // (a unit seed is taken as it is)
                     yb1 += g;
                     const double hg = h * g;
 #pragma unroll

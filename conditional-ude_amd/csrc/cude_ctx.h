@@ -246,6 +246,8 @@ struct cude_ctx {
     cude::api::DevBuf<double> ms_f;    // per-set loss values of a multi-set evaluation
     cude::api::DevBuf<double> sc_rows, sc_sets, sc_state, sc_part;     // cude_subject_scores: rows table, per-set rows, fold state,
     cude::api::DevBuf<int32_t> sc_int;                                 // ... cross-product partials; kept between calls
+    cude::api::DevBuf<double> ni_state, ni_stage;                      // cude_network_information: fold state and matrices, the
+                                                                       // staging of a chunk's rows as [N][outputs][P]
     double scratch_budget = 0.0;       // bytes of scratch one multi-set launch may use (sets_scratch_budget)
     // cude_train_restarts (cude_train.hip): the restarts' optimiser state, resident between iterations
     cude::api::DevBuf<double> tr_m_nn, tr_v_nn, tr_m_cond, tr_v_cond, tr_trace;     // Adam moments [K][P] / [K][N], loss trace
@@ -297,10 +299,12 @@ int32_t maybe_regroup(cude_ctx* c);
 struct SetsRows {
     double* rows;            // [n_sets][P][N]: row of subject i in set k (CpepArgs::lane_rows)
     double* sse;             // [n_sets][N]
+    int32_t unit_seed = 0;   // 1 + l0 > 0: set k's reverse sweep is seeded with 1.0 at live output l0 + k (CpepArgs::unit_seed)
 };
 int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t stride_nn, const double* cond,
                          int64_t stride_cond, double* g_cond, double* out, const SetsRows* rows = nullptr);
 int64_t scores_chunk_sets(cude_ctx* c, int64_t n_sets);
+int64_t info_chunk_sets(cude_ctx* c, int64_t n_live, bool stage);
 // ---- cude_optimise.hip
 void drop_graph(cude_ctx* c);
 int32_t ensure_trace(cude_ctx* c, int64_t n);

@@ -1364,6 +1364,24 @@ __device__ __forceinline__ void store_lane_rows(const A& acc, const double (&cst
     }
 }
 
+// Unit adjoint seed of the kernels compiled with ROWS (Args::unit_seed = 1 + l0 > 0, cude_network_information): set k of the
+// launch seeds live output l0 + k.  The live outputs leave out what depends on no parameter -- the column of t_0, and the
+// suppression model's state 0: c-peptide l -> state 1 at time l + 1; suppression l -> state 1 + l % 2 at time 1 + l / 2.
+template <bool ROWS, class A>
+__device__ __forceinline__ bool unit_seeded(const A& a) {
+    if constexpr (ROWS) return a.unit_seed > 0;
+    else return false;
+}
+template <class A>
+__device__ __forceinline__ double unit_seed_cpep(const A& a, int64_t set, int oi) {
+    return oi == a.unit_seed + (int)set ? 1.0 : 0.0;
+}
+template <class A>
+__device__ __forceinline__ double unit_seed_supp(const A& a, int64_t set, int oi, int state) {
+    const int l = a.unit_seed - 1 + (int)set;
+    return (oi == 1 + (l >> 1) && state == 1 + (l & 1)) ? 1.0 : 0.0;
+}
+
 // block_reduce_expand for a kernel that has kRedWideRows rows of LDS to spare at that point (the fixed-step c-peptide
 // gradient kernels with a layer-1 factor table: cude_cpep.hip).  Every row of a chunk is written TWICE in a row, as 128
 // entries, so lane r finds the entries (l + r) & 63, l = 0 ... 63, of its row at the constant offsets l from one base

@@ -185,6 +185,11 @@ struct GenCpep {
         ob[0] = 2.0 * (o[0] - a.obs[(int64_t)oi * N + i]);
         for (int s = 1; s < NS; s++) ob[s] = 0.0;
     }
+    // ... replaced by the unit seed of set `set` (CpepArgs::unit_seed > 0)
+    __device__ __forceinline__ void unit_bar(const Args& a, int oi, int64_t set, double (&ob)[NS]) const {
+        ob[0] = unit_seed_cpep(a, set, oi);
+        for (int s = 1; s < NS; s++) ob[s] = 0.0;
+    }
     // weight of d out / d (params, inputs) in kb^T f, and the part of J_f^T kb that does not pass through the network
     __device__ __forceinline__ double vjp_linear(const double (&kb)[NS], double (&ub)[NS]) const {
         ub[0] += fma(a11, kb[0], a21 * kb[1]);
@@ -236,6 +241,9 @@ struct GenSupp {
     __device__ __forceinline__ void residual_bar(const Args& a, int oi, const double (&o)[NS], double (&ob)[NS]) const {
         for (int q = 0; q < 3; q++) ob[q] = 2.0 * a.iscale2[q] * (o[q] - a.data[((int64_t)q * a.T + oi) * N + i]);
     }
+    __device__ __forceinline__ void unit_bar(const Args& a, int oi, int64_t set, double (&ob)[NS]) const {
+        for (int q = 0; q < 3; q++) ob[q] = unit_seed_supp(a, set, oi, q);
+    }
     __device__ __forceinline__ double vjp_linear(const double (&kb)[NS], double (&ub)[NS]) const {
         ub[0] += fma(-0.4, kb[0], 0.4 * kb[1]);
         ub[2] += -0.3 * kb[2];
@@ -276,7 +284,9 @@ struct GenSuppOut : GenSupp {
 };
 
 // ---------------------------------------------------------------------------------- the integrator
-template <class M, bool GRAD>
+// ROWS (gradient only): the launch keeps the lanes' rows (Args::lane_rows = gen_acc) and may ask for a unit adjoint seed
+// (Args::unit_seed); a kernel of its own, as cpep_kernel's
+template <class M, bool GRAD, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) void generic_kernel(typename M::Args a, GenNet net) {
     constexpr int NS = M::NS;
     constexpr int TROWS = 2 + NS;                  // tape entry: t_n, dt_n, y_n
@@ -503,6 +513,7 @@ __global__ __launch_bounds__(kBlock) void generic_kernel(typename M::Args a, Gen
                     o[q] = fma(h, v, yn[q]);
                 }
                 m.residual_bar(a, oi, o, ob);
+                if constexpr (ROWS) { if (unit_seeded<ROWS>(a)) m.unit_bar(a, oi, set, ob); }
                 for (int q = 0; q < NS; q++) {
                     const double g = gs * ob[q];
                     yb[q] += g;
@@ -558,7 +569,12 @@ hipError_t launch_generic(const GenNet& net, bool grad, const typename M::Args& 
     if (lds > kGenMaxLds) return hipErrorInvalidValue;
     if (grad && (a.gen_acc == nullptr || a.tape == nullptr)) return hipErrorInvalidValue;
     hipError_t e;
-    if (grad) {
+    if (grad && a.lane_rows != nullptr) {
+        if (lds > 65536 &&
+            (e = hipFuncSetAttribute((const void*)generic_kernel<M, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+            return e;
+        hipLaunchKernelGGL((generic_kernel<M, true, true>), dim3((unsigned)nblocks, n_sets), dim3(kBlock), lds, s, a, net);
+    } else if (grad) {
         if (lds > 65536 &&
             (e = hipFuncSetAttribute((const void*)generic_kernel<M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
             return e;

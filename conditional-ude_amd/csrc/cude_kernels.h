@@ -111,6 +111,14 @@ struct CpepArgs {
                              // kernels know), k > 0 = by bit k of the shader clock, i.e. every 2^k cycles (fixed-step kernel only)
     double* tape;            // adaptive gradient: [n_sets][tape_cap][N] step sizes dt_n of the accepted steps (+ T saved outputs)
     int32_t tape_cap;
+    int32_t unit_seed;       // kernels compiled with ROWS only (cude_network_information): 0 = the reverse sweep is seeded with
+                             // the residuals, as ever; 1 + l0 > 0 = set k seeds LIVE output l0 + k with exactly 1.0 and every
+                             // other output with exactly 0.0 (unit_seed_cpep / unit_seed_supp, cude_device.h), so that the
+                             // lane's row is d yhat_io / d theta and its g_cond d yhat_io / d cond_i.  SSE and failures: as ever.
+                             // HERE, in the four bytes of padding between tape_cap and tape_n, not at the end: the argument
+                             // block keeps its size and every other field its offset, so every kernel that does not read the
+                             // field is the machine code it was (appended, the block grows to 648 bytes and the compiler orders
+                             // the scalar loads of 91 gradient kernels of cude_cpep.hip differently: profiles/jacobian.txt)
     int32_t* tape_n;         // [N] accepted steps per subject of parameter set 0 (forward and gradient launches), or nullptr
     int32_t team;            // adaptive mode, small launches: 0 = a step's five evaluations on five waves (cude_adaptive_team.hip)
                              // where that kernel applies, -1 = never (option "adaptive_team" = 0)
@@ -259,6 +267,7 @@ struct SuppArgs {
     double abstol, reltol;
     double* tape;            // adaptive gradient, as CpepArgs
     int32_t tape_cap;
+    int32_t unit_seed;       // as CpepArgs (in the padding behind tape_cap, likewise)
     int32_t* tape_n;
     double* gen_acc;         // as CpepArgs
     const int32_t* perm;     // as CpepArgs
@@ -575,6 +584,43 @@ hipError_t launch_scores_finish(const ScoresArgs& a, const double* mask, int32_t
 // sum [P] and cross [P][P] over the subjects that did not fail (either null: not wanted); partial: scores_cross_partials doubles
 size_t scores_cross_partials(int64_t N, int P);
 hipError_t launch_scores_cross(const ScoresArgs& a, double* partial, double* sum, double* cross, hipStream_t s);
+// output Jacobians and expected information (cude_network_information, cude_jacobian.hip; the numbered rules in
+// include/cude.h): the running state of the fold, kept in device memory between the launches of a call.  Live output l (the
+// sets of the unit-seeded launches: CpepArgs::unit_seed) is output out_index(l) of the caller's tables.
+struct InfoArgs {
+    int64_t N;
+    int32_t P, n_out, supp;                       // supp: 1 = the suppression model's 3 T outputs, 0 = T c-peptide outputs
+    double w[3];                                  // loss weight of state s (c-peptide: w[1] = 1)
+    double pw;                                    // penalty weight
+    double* b;                                    // [P][N] coupling rows (after the finish: NaN rows of failed subjects)
+    double* d;                                    // [N]
+    double* t;                                    // [P][N] b_i / sqrt(d_i + pw), zero for failed and flat subjects
+    double* jc;                                   // [N][n_out]
+    double* qf;                                   // [N][n_out]
+    int32_t* bad;                                 // [N] outputs whose SSE, row or jc was not finite
+    int32_t* status;                              // [N] bit 1 = failed, bit 2 = flat (written by the finish)
+    const double* mask;                           // [P] parameter mask or null
+    __host__ __device__ int out_index(int l) const { return supp ? 3 * (1 + (l >> 1)) + 1 + (l & 1) : l + 1; }
+    __host__ __device__ double weight(int l) const { return supp ? w[1 + (l & 1)] : w[1]; }
+};
+hipError_t launch_info_replicate(int64_t N, int kn, const double* src, double* dst, hipStream_t s);
+// live outputs [l0, l0 + kn) into the state, in output order: rows [kn][P][N], jc and sse [kn][N]; first: from zero
+hipError_t launch_info_fold(const InfoArgs& a, int kn, int l0, bool first, const double* rows, const double* jc, const double* sse,
+                            hipStream_t s);
+// n_failed: one zeroed int32
+hipError_t launch_info_finish(const InfoArgs& a, int32_t* n_failed, hipStream_t s);
+// src [kn][P][N] -> dst [N][dst_rows][P], set k at row out_index(l0 + k) - out_index(l0) (l0 < 0: row k)
+hipError_t launch_info_transpose(const InfoArgs& a, int kn, int l0, int dst_rows, const double* src, bool apply_mask, double* dst,
+                                 hipStream_t s);
+// partial (info_cross_partials doubles) += the weighted cross products of the live outputs [l0, l0 + kn) over the subjects
+// whose status (null: everybody's) has no failed bit; l0 < 0: one table of weight 1.  Then the blocks' sums -> dst [P][P].
+size_t info_cross_partials(int64_t N, int P);
+hipError_t launch_info_cross(const InfoArgs& a, int kn, int l0, bool first, const double* rows, const int32_t* status,
+                             double* partial, hipStream_t s);
+hipError_t launch_info_cross_finish(const InfoArgs& a, const double* partial, double* dst, hipStream_t s);
+hipError_t launch_info_schur(int P, const double* gn, const double* x, double* schur, hipStream_t s);
+hipError_t launch_info_qform(const InfoArgs& a, int kn, int l0, bool profiled, const double* rows, const double* jc,
+                             const double* cov, hipStream_t s);
 // exact order statistics and the sequential mean of every (subject, output time) column of a multi-set dense-output slab
 // (cude_predictive_bands, cude_predictive.hip).  slab: value of set k, column q at slab[k * set_stride + q * col_stride];
 // columns q in [0, n_cols) with q = j + Tc * (subject - first subject of the launch), j the time inside the chunk

@@ -754,6 +754,7 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
         a.sse = rows->sse + k0 * N;
         a.lane_rows = rows->rows + k0 * (int64_t)P * N;
         if (gen) a.gen_acc = a.lane_rows;
+        a.unit_seed = rows->unit_seed > 0 ? rows->unit_seed + (int32_t)k0 : 0;
     };
     for (int64_t k0 = 0; k0 < n_sets; k0 += chunk) {
         const int64_t kn = std::min<int64_t>(chunk, n_sets - k0);
@@ -823,6 +824,15 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
 int64_t scores_chunk_sets(cude_ctx* c, int64_t n_sets) {
     const double per_set = 8.0 * ((double)c->P + 4.0) * (double)c->N;
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_sets, 32768), (int64_t)(0.5 * sets_scratch_budget(c) / per_set)));
+    if (c->opt.profile_chunk > 0) chunk = std::min<int64_t>(chunk, c->opt.profile_chunk);
+    return chunk;
+}
+
+// Live outputs per eval_sets_device call of cude_network_information: as scores_chunk_sets, with the staging of the rows as
+// [N][outputs][P] (up to 3 output rows per 2 live outputs) when the caller wants the Jacobian itself
+int64_t info_chunk_sets(cude_ctx* c, int64_t n_live, bool stage) {
+    const double per_set = 8.0 * ((stage ? 2.5 : 1.0) * (double)c->P + 3.0) * (double)c->N;
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_live, 32768), (int64_t)(0.5 * sets_scratch_budget(c) / per_set)));
     if (c->opt.profile_chunk > 0) chunk = std::min<int64_t>(chunk, c->opt.profile_chunk);
     return chunk;
 }
@@ -1382,6 +1392,164 @@ int32_t cude_subject_scores(cude_ctx* c, int32_t n_sets, const double* cond_sets
     HIP_TRY(hipMemcpyAsync(&failed, d_nfail, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->last_failed = failed;
+    return CUDE_OK;
+}
+
+int32_t cude_n_outputs(cude_ctx* c, int32_t* n_out) {
+    if (!c || !n_out) return fail(CUDE_ERR_ARG, "null argument");
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    *n_out = is_cpep(c) ? c->T : 3 * c->T;
+    return CUDE_OK;
+}
+
+int32_t cude_network_information(cude_ctx* c, const double* cond, double penalty_weight, const double* cov, int32_t profiled,
+                                 double* jac_out, double* jcond_out, double* gn_out, double* coupling_out, double* dcond_out,
+                                 double* schur_out, double* qform_out, int32_t* status_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (!cond && !c->have_cond) return fail(CUDE_ERR_STATE, "cond is NULL and the conditional parameters are not set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_network_information under stream capture");
+    if (!jac_out && !jcond_out && !gn_out && !coupling_out && !dcond_out && !schur_out && !qform_out && !status_out)
+        return fail(CUDE_ERR_ARG, "no output requested");
+    if (qform_out && !cov) return fail(CUDE_ERR_ARG, "qform_out needs cov");
+    if (!(penalty_weight >= 0.0) || !std::isfinite(penalty_weight))
+        return fail(CUDE_ERR_ARG, "penalty_weight must be finite and >= 0");
+    const int P = c->P;
+    const int64_t N = c->N;
+    if (cov && qform_out)
+        for (int64_t j = 0; j < (int64_t)P * P; j++)
+            if (!std::isfinite(cov[j])) return fail(CUDE_ERR_ARG, "cov must be finite");
+    const bool cpep = is_cpep(c);
+    const int T = c->T, n_out = cpep ? T : 3 * T;
+    const int n_live = cpep ? T - 1 : 2 * (T - 1);
+    const bool want_a = gn_out || schur_out, want_q = qform_out != nullptr;
+    const int64_t chunk = n_live > 0 ? info_chunk_sets(c, n_live, jac_out != nullptr) : 1;
+    const bool single = chunk >= n_live;
+    const int span_max = cpep ? (int)chunk : 3 * (((int)chunk + 1) / 2) + 2;
+    const size_t n_part = cude::info_cross_partials(N, P);
+    // per-set rows of a launch: conditionals, SSEs, conditional gradients; state: b, t [P][N], d [N], jc, qf [N][n_out], the
+    // coupling table as [N][P], gn / the Schur term / schur / cov [P][P], the conditional vector [N], two sets of partials
+    HIP_TRY(c->sc_rows.reserve((size_t)chunk * P * N));
+    HIP_TRY(c->sc_sets.reserve((size_t)chunk * 3 * N));
+    HIP_TRY(c->ni_state.reserve((size_t)(3 * P + 2 + 2 * n_out) * N + (size_t)4 * P * P + 2 * n_part));
+    HIP_TRY(c->sc_int.reserve((size_t)2 * N + 1));
+    HIP_TRY(c->ms_out.reserve((size_t)chunk * (P + 2)));
+    if (jac_out) HIP_TRY(c->ni_stage.reserve((size_t)N * span_max * P));
+    double* const d_cond = c->sc_sets.p;
+    double* const d_sse = d_cond + chunk * N;
+    double* const d_gcond = d_sse + chunk * N;
+    cude::InfoArgs ia{};
+    ia.N = N; ia.P = P; ia.n_out = n_out; ia.supp = cpep ? 0 : 1;
+    for (int s = 0; s < 3; s++) ia.w[s] = cpep ? 1.0 : 1.0 / (c->scale[s] * c->scale[s]);
+    ia.pw = penalty_weight;
+    ia.b = c->ni_state.p; ia.t = ia.b + (size_t)P * N; ia.d = ia.t + (size_t)P * N;
+    ia.jc = ia.d + N; ia.qf = ia.jc + (size_t)n_out * N;
+    double* const d_coup = ia.qf + (size_t)n_out * N;
+    double* const d_cond0 = d_coup + (size_t)P * N;
+    double* const d_gn = d_cond0 + N;
+    double* const d_x = d_gn + (size_t)P * P;
+    double* const d_schur = d_x + (size_t)P * P;
+    double* const d_cov = d_schur + (size_t)P * P;
+    double* const d_part = d_cov + (size_t)P * P;
+    double* const d_partx = d_part + n_part;
+    ia.bad = c->sc_int.p; ia.status = ia.bad + N;
+    int32_t* const d_nfail = ia.status + N;
+    ia.mask = c->param_mask.p;
+    const double* cond0 = c->cond.p;
+    if (cond) {
+        HIP_TRY(hipMemcpyAsync(d_cond0, cond, N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        cond0 = d_cond0;
+    }
+    HIP_TRY(cude::launch_info_replicate(N, (int)chunk, cond0, d_cond, c->stream));
+    if (want_q) HIP_TRY(hipMemcpyAsync(d_cov, cov, (size_t)P * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the rows of t_0 and of suppression state 0 depend on no parameter: +0.0 without a launch
+    HIP_TRY(hipMemsetAsync(ia.jc, 0, (size_t)2 * n_out * N * sizeof(double), c->stream));
+    if (jac_out) std::memset(jac_out, 0, (size_t)N * n_out * P * sizeof(double));
+    SetsRows rows{c->sc_rows.p, d_sse, 0};
+    const auto solve = [&](int l0, int kn) {
+        rows.unit_seed = 1 + l0;
+        return eval_sets_device(c, kn, c->nn.p, 0, d_cond, N, d_gcond, c->ms_out.p, &rows);
+    };
+    if (n_live == 0) {       // (a population with one time point: the fold of nothing)
+        HIP_TRY(hipMemsetAsync(ia.b, 0, (size_t)(2 * P + 1) * N * sizeof(double), c->stream));
+        HIP_TRY(hipMemsetAsync(ia.bad, 0, (size_t)N * sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(d_part, 0, n_part * sizeof(double), c->stream));
+    }
+    // ---- first pass: b, d, the failures; the caller's Jacobian chunk by chunk.  With several chunks A is summed along in
+    // the hope that no subject fails (the second pass needs every launch again)
+    const bool a_along = want_a && !single && !want_q;
+    for (int l0 = 0; l0 < n_live; l0 += (int)chunk) {
+        const int kn = (int)std::min<int64_t>(chunk, n_live - l0);
+        if ((rc = solve(l0, kn))) return rc;
+        HIP_TRY(cude::launch_info_fold(ia, kn, l0, l0 == 0, c->sc_rows.p, d_gcond, d_sse, c->stream));
+        if (a_along) HIP_TRY(cude::launch_info_cross(ia, kn, l0, l0 == 0, c->sc_rows.p, nullptr, d_part, c->stream));
+        if (jac_out) {
+            const int o0 = ia.out_index(l0), span = ia.out_index(l0 + kn - 1) - o0 + 1;
+            HIP_TRY(hipMemsetAsync(c->ni_stage.p, 0, (size_t)N * span * P * sizeof(double), c->stream));
+            HIP_TRY(cude::launch_info_transpose(ia, kn, l0, span, c->sc_rows.p, true, c->ni_stage.p, c->stream));
+            HIP_TRY(hipMemcpy2DAsync(jac_out + (size_t)o0 * P, (size_t)n_out * P * sizeof(double), c->ni_stage.p,
+                                     (size_t)span * P * sizeof(double), (size_t)span * P * sizeof(double), (size_t)N,
+                                     hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipMemsetAsync(d_nfail, 0, sizeof(int32_t), c->stream));
+    HIP_TRY(cude::launch_info_finish(ia, d_nfail, c->stream));
+    int32_t failed = 0;
+    HIP_TRY(hipMemcpyAsync(&failed, d_nfail, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // ---- second pass: A over the subjects that did not fail, and the quadratic forms (they need b and d complete).  One
+    // chunk: its rows are still there.  Several: the launches run again -- for the quadratic forms always, for A only where
+    // a subject failed, which the host has to ask the device about
+    bool again = want_q || (want_a && single);
+    if (a_along) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        again = failed > 0;
+    }
+    if (again) {
+        for (int l0 = 0; l0 < n_live; l0 += (int)chunk) {
+            const int kn = (int)std::min<int64_t>(chunk, n_live - l0);
+            if (!single && (rc = solve(l0, kn))) return rc;
+            if (want_a) HIP_TRY(cude::launch_info_cross(ia, kn, l0, l0 == 0, c->sc_rows.p, ia.status, d_part, c->stream));
+            if (want_q) HIP_TRY(cude::launch_info_qform(ia, kn, l0, profiled != 0, c->sc_rows.p, d_gcond, d_cov, c->stream));
+        }
+    }
+    if (want_a) HIP_TRY(cude::launch_info_cross_finish(ia, d_part, d_gn, c->stream));
+    if (schur_out) {
+        HIP_TRY(cude::launch_info_cross(ia, 1, -1, true, ia.t, ia.status, d_partx, c->stream));
+        HIP_TRY(cude::launch_info_cross_finish(ia, d_partx, d_x, c->stream));
+        HIP_TRY(cude::launch_info_schur(P, d_gn, d_x, d_schur, c->stream));
+    }
+    if (coupling_out) {
+        HIP_TRY(cude::launch_info_transpose(ia, 1, -1, 1, ia.b, false, d_coup, c->stream));
+        HIP_TRY(hipMemcpyAsync(coupling_out, d_coup, (size_t)P * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (jcond_out) HIP_TRY(hipMemcpyAsync(jcond_out, ia.jc, (size_t)n_out * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (qform_out) HIP_TRY(hipMemcpyAsync(qform_out, ia.qf, (size_t)n_out * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (dcond_out) HIP_TRY(hipMemcpyAsync(dcond_out, ia.d, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (gn_out) HIP_TRY(hipMemcpyAsync(gn_out, d_gn, (size_t)P * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (schur_out) HIP_TRY(hipMemcpyAsync(schur_out, d_schur, (size_t)P * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    std::vector<int32_t> st_host;
+    std::vector<double> mask_host;
+    int32_t* st = status_out;
+    if (jac_out && !st) { st_host.resize((size_t)N); st = st_host.data(); }
+    if (st) HIP_TRY(hipMemcpyAsync(st, ia.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (jac_out && ia.mask) {
+        mask_host.resize((size_t)P);
+        HIP_TRY(hipMemcpyAsync(mask_host.data(), ia.mask, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_failed = failed;
+    // (a failure shows only once every output is in, and the Jacobian's chunks have left the device by then)
+    if (jac_out && failed > 0) {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t i = 0; i < N; i++) {
+            if (!(st[i] & 1)) continue;
+            double* row = jac_out + (size_t)i * n_out * P;
+            for (int o = 0; o < n_out; o++)
+                for (int q = 0; q < P; q++) row[(size_t)o * P + q] = (!mask_host.empty() && mask_host[q] == 0.0) ? 0.0 : nan;
+        }
+    }
     return CUDE_OK;
 }
 

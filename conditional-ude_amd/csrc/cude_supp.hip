@@ -359,7 +359,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(supp_wav
                     double hg[2];
 #pragma unroll
                     for (int s = 0; s < 2; s++) {
-                        const double g = gs * a.iscale2[s + 1] * res[(int64_t)(oi * 2 + s) * N + i];
+                        double g = gs * a.iscale2[s + 1] * res[(int64_t)(oi * 2 + s) * N + i];
+                        if constexpr (ROWS) { if (unit_seeded<ROWS>(a)) g = unit_seed_supp(a, set, oi, s + 1); }
                         YB(s) += g;
                         hg[s] = h * g;
                     }

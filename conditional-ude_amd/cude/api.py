@@ -1600,18 +1600,135 @@ def opg_covariance(opg):
     return cov, np.sqrt(np.clip(np.diag(cov), 0.0, None))
 
 
-def network_standard_errors(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, **kwargs):
-    """Standard errors of the network parameters from the cross-product (OPG, "S matrix") estimator of the information:
+def network_standard_errors(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, estimator="opg",
+                            **kwargs):
+    """Standard errors of the network parameters.  estimator = "expected": from the expected (Gauss-Newton) information with
+    the conditionals fitted, cov = sigma^2 pinv(S) with S network_information's schur under the prior omega (rank at most N
+    (T - 1) - N); returns a namespace cov, se, schur, gn, rank, n_failed (prior_mean is not used; n_steps is the only further
+    keyword).  estimator = "opg" (the default), from the cross-product (OPG, "S matrix") estimator of the information:
     opg = sum_i g_i g_i^T with g_i = subject i's gradient of its MARGINAL log-likelihood (marginal_score, same arguments),
     cov = pinv(opg), se = sqrt(diag(cov)).  Returns a namespace: cov (P, P), se (P,), opg, rank, gradient, total.
     The rank of opg is at most N, the number of subjects: with fewer subjects than parameters the pseudo-inverse covers
     the span of the scores only, and se is 0 outside it (rank tells).  Scores taken at fitted conditionals instead
     (subject_scores: the K = 1 table) would ignore the uncertainty of the conditionals and understate these errors; this
     function does not use them."""
+    if estimator == "expected":
+        info = network_information(betas, nn, models, timepoints, cpeptide_data, sigma=sigma, prior_omega=omega,
+                                   n_steps=kwargs.pop("n_steps", None))
+        if kwargs:
+            raise TypeError(f"estimator='expected' takes no {sorted(kwargs)}")
+        cov = float(sigma) ** 2 * _pinv_sym(info["schur"])
+        return SimpleNamespace(cov=cov, se=np.sqrt(np.clip(np.diag(cov), 0.0, None)), schur=info["schur"], gn=info["gn"],
+                               rank=int(np.linalg.matrix_rank(info["schur"], hermitian=True)), n_failed=info["n_failed"])
+    if estimator != "opg":
+        raise ValueError(f"estimator must be 'opg' or 'expected', got {estimator!r}")
     ms = marginal_score(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, **kwargs)
     cov, se = opg_covariance(ms.opg)
     return SimpleNamespace(cov=cov, se=se, opg=ms.opg, rank=int(np.linalg.matrix_rank(ms.opg, hermitian=True)),
                            gradient=ms.gradient, total=ms.total)
+
+
+# ----------------------------------------------------------------------------- expected information (Gauss-Newton)
+def _params_set(theta, args, n_steps):
+    """The population of args = (models, timepoints, cpeptide_data) with theta's parameters set, as subject_scores."""
+    models, timepoints, data = args
+    if _is_model(models):
+        models, data = [models], np.asarray(data)[None, :]
+    if isinstance(models[0], CPeptideODEModel):
+        pop = _population(models, timepoints, data, n_steps, cond_space="raw")
+        nn = getattr(theta, "neural", None)
+        cond = getattr(theta, "conditional", getattr(theta, "ode", theta))
+        pop.engine.set_params(pop.shared if nn is None else nn, np.asarray(cond, dtype=np.float64).reshape(-1)[:pop.N])
+    else:
+        pop = _population(models, timepoints, data, n_steps)
+        pop.engine.set_params(theta.neural, np.asarray(theta.conditional, dtype=np.float64).reshape(-1)[:pop.N])
+    return pop
+
+
+def output_jacobian(theta, args, *, n_steps=None):
+    """(jac (N, T, P), jcond (N, T)): the derivative of every subject's predicted c-peptide at the data's times with respect
+    to the shared parameters theta.neural and to its own conditional parameter, at theta (cude_network_information); args =
+    (models, timepoints, cpeptide_data) as `loss`.  The column of t_0 is exactly zero; rows of failed subjects are NaN."""
+    out = _params_set(theta, args, n_steps).engine.network_information(want=("jac", "jcond"))
+    return out["jac"], out["jcond"]
+
+
+def _penalty_weight(sigma, prior_omega):
+    return 0.0 if prior_omega is None else (float(sigma) / float(prior_omega)) ** 2
+
+
+def _information(eng, pw):
+    out = eng.network_information(penalty_weight=pw, want=("gn", "schur", "coupling", "dcond", "status"))
+    out = {k: out[k] for k in ("gn", "schur", "coupling", "dcond", "status")}
+    out["penalty_weight"], out["n_failed"] = pw, eng.n_failed()
+    return out
+
+
+def network_information(betas, nn, models, timepoints, cpeptide_data, *, sigma, prior_omega=None, n_steps=None):
+    """Expected-information (Gauss-Newton) matrices of the network parameters at the fitted conditionals betas: dict(gn (P,
+    P) = A = sum_i J_i^T J_i, the information with the conditionals taken as known; schur (P, P) = A - sum_i b_i b_i^T / (d_i
+    + pw), the information with the conditionals fitted (the Schur complement of the arrowhead matrix); coupling (N, P) =
+    b_i; dcond (N,) = d_i; status (N,): bit 1 failed, bit 2 flat; penalty_weight; n_failed), all in units of 1 / sigma^2.
+    pw = sigma^2 / prior_omega^2 when the conditionals have a Gaussian prior of standard deviation prior_omega, else 0."""
+    theta = ComponentArray(neural=nn, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
+    pop = _params_set(theta, (models, timepoints, cpeptide_data), n_steps)
+    return _information(pop.engine, _penalty_weight(sigma, prior_omega))
+
+
+def _pinv_sym(m, rcond=1e-12):
+    """Pseudo-inverse of a symmetric information matrix.  S = A - sum_i t_i t_i^T is rank-deficient whenever P exceeds N (n_out
+    - 2), and its null directions come out of the subtraction as rounding residue of the order of 1e-16 of the largest
+    eigenvalue: eigenvalues below rcond of the largest are taken as zero."""
+    m = np.asarray(m, dtype=np.float64)
+    return np.linalg.pinv(0.5 * (m + m.T), rcond=rcond, hermitian=True)
+
+
+def network_covariance(betas, nn, models, timepoints, cpeptide_data, *, sigma, prior_omega=None, n_steps=None):
+    """sigma^2 pinv(S): the covariance of the network parameters from the expected information with the conditionals
+    fitted (network_information's schur)."""
+    info = network_information(betas, nn, models, timepoints, cpeptide_data, sigma=sigma, prior_omega=prior_omega,
+                               n_steps=n_steps)
+    return float(sigma) ** 2 * _pinv_sym(info["schur"])
+
+
+def _prediction_se(eng, sigma, pw):
+    """(se (N, n_out), info): a first call for S, a second with cov = pinv(S) and profiled rows."""
+    info = _information(eng, pw)
+    out = eng.network_information(penalty_weight=pw, cov=_pinv_sym(info["schur"]), profiled=True,
+                                  want=("jcond", "dcond", "qform", "status"))
+    den = out["dcond"] + pw
+    flat = (out["status"] & 2) != 0
+    own = np.where(flat[:, None], 0.0, out["jcond"] ** 2 / np.where(flat, 1.0, den)[:, None])
+    return float(sigma) * np.sqrt(np.clip(out["qform"] + own, 0.0, None)), info
+
+
+def prediction_standard_errors(betas, nn, models, timepoints, cpeptide_data, *, sigma, prior_omega=None, n_steps=None):
+    """Delta-method standard errors (N, T) of the predicted c-peptide curves at the data's times, the closed-form companion
+    of posterior_predictive: se_io = sigma sqrt(z S^+ z^T + jc_io^2 / (d_i + pw)), z = J_io - jc_io / (d_i + pw) b_i -- the
+    variance of yhat_io under the joint Gauss-Newton covariance of the network and subject i's own conditional.  Exactly
+    zero at t_0; NaN for failed subjects; a flat subject (status bit 2) contributes the network's term alone."""
+    theta = ComponentArray(neural=nn, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
+    pop = _params_set(theta, (models, timepoints, cpeptide_data), n_steps)
+    return _prediction_se(pop.engine, sigma, _penalty_weight(sigma, prior_omega))[0]
+
+
+def suppression_output_jacobian(p, args, *, n_steps=None):
+    """output_jacobian for the suppression model: args = (prob, individual_data, timepoints, lambda) as suppression_loss.
+    Returns (jac (N, 3 T, P), jcond (N, 3 T)) with output o = s + 3 j (state s at time j); the rows of state 0 and of t_0
+    are exactly zero."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, p.theta)
+    out = pop.engine.network_information(want=("jac", "jcond"))
+    return out["jac"], out["jcond"]
+
+
+def suppression_network_information(p, args, *, sigma=1.0, prior_omega=None, n_steps=None):
+    """network_information for the suppression model, with the loss's weights 1 / scale_s^2 on the outputs of state s."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, p.theta)
+    return _information(pop.engine, _penalty_weight(sigma, prior_omega))
 
 
 def _marginal_em_rounds(x0, hyper0, objective, update, rounds, iterations):

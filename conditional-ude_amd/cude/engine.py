@@ -490,6 +490,45 @@ class Engine:
                                             _ptr(out["bad"]), _ptr(out["sum"]), _ptr(out["cross"])))
         return out
 
+    @property
+    def n_outputs(self):
+        """Outputs per subject of network_information (cude_n_outputs): T for the c-peptide models, 3 T for suppression."""
+        n = C.c_int32()
+        check(self._lib.cude_n_outputs(self._h, C.byref(n)))
+        return n.value
+
+    INFO_OUTPUTS = ("jac", "jcond", "gn", "coupling", "dcond", "schur", "qform", "status")
+
+    def network_information(self, cond=None, penalty_weight=0.0, cov=None, profiled=False,
+                            want=("gn", "coupling", "dcond", "schur", "status")):
+        """Output Jacobians with respect to the shared parameters and the expected-information matrices on the device
+        (cude_network_information): cond (N,) -- None: the context's conditional parameters.  Returns dict(jac (N, n_out, P)
+        = d yhat_io / d theta, jcond (N, n_out) = d yhat_io / d cond_i, gn (P, P) = A, coupling (N, P) = b_i, dcond (N,) =
+        d_i, schur (P, P) = A - sum_i b_i b_i^T / (d_i + penalty_weight), qform (N, n_out) = z cov z^T (needs cov; z = J_io
+        - jc_io / (d_i + pw) b_i when profiled, J_io otherwise), status (N,) int32: bit 1 failed, bit 2 flat), None for
+        what `want` leaves out.  A failed subject has NaN rows, is left out of gn and schur, and is counted by n_failed()
+        afterwards."""
+        unknown = set(want) - set(self.INFO_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        cd = None if cond is None else _f64(cond).reshape(-1)
+        if cd is not None and cd.size != self.N:
+            raise ValueError(f"expected cond ({self.N},)")
+        P, N = self.P, self.N
+        cv = None if cov is None else _f64(cov)
+        if cv is not None and cv.shape != (P, P):
+            raise ValueError(f"expected cov ({P}, {P})")
+        n_out = self.n_outputs
+        shapes = {"jac": (N, n_out, P), "jcond": (N, n_out), "gn": (P, P), "coupling": (N, P), "dcond": (N,),
+                  "schur": (P, P), "qform": (N, n_out), "status": (N,)}
+        out = {k: (np.empty(shapes[k], dtype=np.int32 if k == "status" else np.float64) if k in want else None)
+               for k in self.INFO_OUTPUTS}
+        check(self._lib.cude_network_information(self._h, _ptr(cd), float(penalty_weight), _ptr(cv), 1 if profiled else 0,
+                                                 _ptr(out["jac"]), _ptr(out["jcond"]), _ptr(out["gn"]),
+                                                 _ptr(out["coupling"]), _ptr(out["dcond"]), _ptr(out["schur"]),
+                                                 _ptr(out["qform"]), _ptr(out["status"])))
+        return out
+
     def fit_conditional(self, lower, upper, n_grid=41, n_iters=48, penalty_weight=0.0, penalty_center=0.0):
         """All subjects' 1-D fits of the conditional parameter with the shared parameters frozen, on the device:
         argmin_x SSE_i(x) + penalty_weight (x - penalty_center)^2 over [lower, upper] -> (x[N], objective[N], sse[N])."""

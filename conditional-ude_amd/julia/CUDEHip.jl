@@ -30,7 +30,8 @@ export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEMod
        profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
-       marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores
+       marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores,
+       network_information, n_outputs
 
 const LIB = get(ENV, "CUDE_HIP_LIB", "libcude_hip.so")
 const MODEL_CPEP, MODEL_SUPP, MODEL_CPEP_SYM = Int32(0), Int32(1), Int32(2)
@@ -345,6 +346,35 @@ function subject_scores(c::Ctx; cond_sets = nothing, weights = nothing)
         (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
         c.h, Int32(K), x === nothing ? C_NULL : pointer(x), w === nothing ? C_NULL : pointer(w), scores, wsse, bad, total, cross))
     scores, wsse, bad, total, cross
+end
+
+# outputs per subject of network_information: T for the c-peptide models, 3T for the suppression model
+function n_outputs(c::Ctx)
+    n = Ref{Int32}(0)
+    check(ccall((:cude_n_outputs, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), c.h, n))
+    Int(n[])
+end
+
+# output Jacobians ∂ŷᵢₒ/∂θ and the expected-information matrices built from them (cude_network_information): cond = nothing:
+# the context's conditional parameters; cov (P×P) = nothing: no quadratic forms.  Returns a named tuple: jac P×n_out×N
+# (only with want_jac), jcond n_out×N, gn P×P = A, coupling P×N = bᵢ, dcond = dᵢ, schur P×P = A − Σᵢ bᵢbᵢᵀ/(dᵢ + pw), qform
+# n_out×N or nothing, status (bit 1 failed, bit 2 flat).  A failed subject has NaN columns and is left out of gn and schur
+function network_information(c::Ctx; cond = nothing, penalty_weight = 0.0, cov = nothing, profiled = false, want_jac = false)
+    n_out = n_outputs(c)
+    x = cond === nothing ? nothing : Vector{Float64}(cond)
+    C = cov === nothing ? nothing : Matrix{Float64}(cov)
+    jac = want_jac ? Array{Float64}(undef, c.P, n_out, c.N) : nothing
+    jcond = Matrix{Float64}(undef, n_out, c.N); gn = Matrix{Float64}(undef, c.P, c.P)
+    coupling = Matrix{Float64}(undef, c.P, c.N); dcond = Vector{Float64}(undef, c.N)
+    schur = Matrix{Float64}(undef, c.P, c.P); status = Vector{Int32}(undef, c.N)
+    qform = C === nothing ? nothing : Matrix{Float64}(undef, n_out, c.N)
+    GC.@preserve x C jac jcond gn coupling dcond schur qform status check(ccall((:cude_network_information, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Float64, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        c.h, x === nothing ? C_NULL : pointer(x), Float64(penalty_weight), C === nothing ? C_NULL : pointer(C),
+        Int32(profiled ? 1 : 0), jac === nothing ? C_NULL : pointer(jac), jcond, gn, coupling, dcond, schur,
+        qform === nothing ? C_NULL : pointer(qform), status))
+    (; jac, jcond, gn, coupling, dcond, schur, qform, status)
 end
 
 adam_init!(c::Ctx, η; β1 = 0.9, β2 = 0.999, ϵ = 1e-8) =

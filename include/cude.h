@@ -520,6 +520,66 @@ int32_t cude_marginal_likelihood(cude_ctx* ctx, int32_t n_nodes, const double* n
 int32_t cude_subject_scores(cude_ctx* ctx, int32_t n_sets, const double* cond_sets, const double* weights,
                             double* score_out, double* wsse_out, int32_t* bad_out, double* sum_out, double* cross_out);
 
+/* Output Jacobians with respect to the shared (network) parameters and the expected-information (Gauss-Newton) matrices of
+ * a least-squares fit built from them.  With J_io = d yhat_io / d theta [P] and jc_io = d yhat_io / d cond_i for subject i and
+ * output o, and the loss's own weights w_o:
+ *   A   = sum_i sum_o w_o J_io^T J_io            [P][P]  information for theta with the conditionals taken as known
+ *   b_i = sum_o w_o jc_io J_io                   [P]     coupling of theta with subject i's own conditional parameter
+ *   d_i = sum_o w_o jc_io^2                              (cude_sensitivity's info)
+ *   S   = A - sum_i b_i b_i^T / (d_i + pw)       [P][P]  Schur complement of the arrowhead matrix [[A, B], [B^T, D + pw I]]:
+ *                                                        the information for theta with the conditionals fitted
+ *   qform_io = z C z^T, z = J_io - (profiled ? jc_io / (d_i + pw) : 0) b_i: with C = pinv(S) and profiled = 1,
+ *              qform_io + jc_io^2 / (d_i + pw) is the delta-method variance of yhat_io in units of sigma^2.
+ * The rank of A is bounded by N (n_out - 1), not by N as the rank of cude_subject_scores' cross product is.
+ *   1. Outputs: c-peptide models (n_state 2 or 3) n_out = T, o = j: state 1 at the data's time j, w_o = 1.  Suppression
+ *      model n_out = 3 T, o = s + 3 j (the order of cude_forward's traj), w_o = 1 / scale_s^2.  cude_n_outputs reports n_out.
+ *      The rows of the column t_0, and every row of suppression state 0, depend on no parameter: exactly +0.0, and no launch
+ *      is spent on them.
+ *   2. Rows: the live outputs are the sets of multi-set gradient launches on the one-lane kernels (as cude_subject_scores
+ *      rule 1), whose reverse sweep is seeded with exactly 1.0 at that output and exactly 0.0 elsewhere instead of the
+ *      residuals: the lane's row is J_io and its conditional gradient jc_io, in the state's own units (no 2, no 1/N, no
+ *      1/scale^2).  Adaptive mode: the derivative of the accepted-step map, the adjoint's convention.  cond [N] = the
+ *      conditional vector of every launch, replicated on the device; NULL = the context's.
+ *   3. Launch shape: live outputs per launch by the scratch budget and option "profile_chunk".  b_i and d_i are folded by one
+ *      lane per (subject, parameter) in output order o = 0 ... n_out - 1 from 0, s = s + ((w_o jc_io) J_io) with every
+ *      product and the sum rounded on their own (no fma contraction), in state that lives in device memory between the
+ *      launches: every output of the call is bit-identical for every chunking.
+ *      Cost: with ONE chunk the launches run once.  With several, qform_out needs b_i and d_i complete before the rows are
+ *      read again, so the launches run a second time; without qform_out, A is summed along the first pass, the call
+ *      synchronises once in between to learn whether a subject failed, and only then runs the launches again for A.
+ *   4. A and S are summed over the subjects that did not fail with plain FMAs in an order fixed by (N, n_out) alone: blocks of
+ *      1024 subjects; inside a block the outputs in order, inside an output the subjects in index order, acc = fma(w_o J_q,
+ *      J_r, acc); then the blocks in block order.  Both triangles are written and equal bit for bit.  The Schur term is the
+ *      same sum over t_i = b_i / sqrt(d_i + pw), and S = A - that, entry by entry.
+ *   5. FLAT (status bit 2): a subject whose d_i + pw is not > 0.  Its Schur term is skipped, its qform uses z = J_io, and it
+ *      is not a failure.
+ *   6. FAILED (status bit 1): a subject with a non-finite row entry, jc or SSE of the solve at any live output (or a b_i / d_i
+ *      that overflowed).  Every entry of its jac and jcond rows (masked columns: 0), coupling, dcond and qform is NaN; it is
+ *      left out of A and S and counted by cude_n_failed afterwards.  Other subjects are unaffected, bit for bit.
+ *   7. Parameter mask (cude_set_param_mask): every row is multiplied by it; a masked entry is exactly +0.0 in jac_out,
+ *      coupling_out, and the rows and columns of gn_out and schur_out.
+ *   8. Both network models, the symbolic model (P = 1) in either cond_space, fixed-step and adaptive mode, every tuned shape
+ *      with any of its activation functions, and the fallback kernel.  Adaptive mode: cude_adaptive_steps refuses afterwards;
+ *      a population of 8192 subjects or more may be regrouped as by cude_subject_scores (rule 7 there).
+ *   9. Sharded population: A and S are this rank's sums (with this rank's Schur terms); they are additive over the ranks.
+ *  10. CUDE_ERR_ARG: no output requested, qform_out without cov, a non-finite cov entry, penalty_weight negative or not
+ *      finite.  CUDE_ERR_STATE: no population or shared parameters, cond == NULL without conditional parameters, stream
+ *      capture.
+ *  11. Leaves the context's parameters untouched.  Everything is queued on the context's stream; one synchronisation at the
+ *      end (and the one of rule 3).  jac_out is written chunk by chunk.
+ * Outputs (all optional, at least one): jac_out [N][n_out][P], jcond_out [N][n_out], gn_out [P][P], coupling_out [N][P],
+ * dcond_out [N], schur_out [P][P], qform_out [N][n_out] (needs cov [P][P], finite), status_out [N].
+ * Not built: a trainer on these matrices; sharing one forward solve among the outputs of a subject (every output's launch
+ * row repeats it); an MFMA cross product; rows from the time-split and five-wave kernels; output times other than the
+ * data's. */
+#define CUDE_INFO_FAILED 1
+#define CUDE_INFO_FLAT 2
+int32_t cude_network_information(cude_ctx* ctx, const double* cond, double penalty_weight, const double* cov, int32_t profiled,
+                                 double* jac_out, double* jcond_out, double* gn_out, double* coupling_out, double* dcond_out,
+                                 double* schur_out, double* qform_out, int32_t* status_out);
+/* Outputs per subject of cude_network_information (rule 1).  CUDE_ERR_STATE: no population. */
+int32_t cude_n_outputs(cude_ctx* ctx, int32_t* n_out);
+
 /* SAEM E-step on the device: n_mc Metropolis-Hastings steps of every subject's conditional parameter
  * (`mcmc_step` src/saem.jl:86-108, applied n_mcmc_steps times with the stochastic-approximation update of the
  * chain state :177-186).  The chain state is the context's conditional parameters (updated in place); the
