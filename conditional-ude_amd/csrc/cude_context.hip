@@ -206,6 +206,7 @@ const OptionEntry kOptions[] = {
     {"graph_unroll", "CUDE_GRAPH_UNROLL", &Options::graph_unroll, false, true},
     {"prio_shift", "CUDE_PRIO_SHIFT", &Options::prio_shift, false, true},
     {"prio_clock", "CUDE_PRIO_CLOCK", &Options::prio_clock, false, true},
+    {"lean_clamp", "CUDE_LEAN_CLAMP", &Options::lean_clamp, false, false},
     {"dense_chunk", "CUDE_DENSE_CHUNK", &Options::dense_chunk, false, false},
     {"dense_layout", "CUDE_DENSE_LAYOUT", &Options::dense_layout, false, false},
     {"refine_fused", "CUDE_REFINE_FUSED", &Options::refine_fused, false, false},

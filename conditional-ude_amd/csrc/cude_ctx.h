@@ -111,6 +111,8 @@ struct Options {
     int prio_shift = -1;        // CUDE_PRIO_SHIFT (-1 = the rule in prio_shift_for)
     int prio_clock = -1;        // CUDE_PRIO_CLOCK: the launches that alternate do so by their own progress (0) or by the shader clock,
                                 //   period 2^k cycles (k > 0); -1 = the rule in prio_clock_for
+    int lean_clamp = -1;        // CUDE_LEAN_CLAMP: -1 = the fixed-step gradient kernel's waves drop the clamps their parameter set
+                                //   proves dead (CpepArgs::lean_clamp, the kernel's own test); 0 = always the clamped sweeps
 };
 
 // Peer-write exchange (cude_comm.hip): this rank's mailbox, every rank's mailbox as mapped here, per-column sequence

@@ -117,20 +117,23 @@ __device__ __forceinline__ void bias_lds_init(const double* p, int lane) {
     __syncthreads();
 }
 
-template <int W, bool TT>
+// LEAN (exponential form only): without the clamp of |z| at 20 -- layers whose weights bound |z| (m_lean_bounds)
+template <int W, bool TT, bool LEAN = false>
 __device__ __forceinline__ void act_tanh_vec(const double (&z)[W], double (&t)[W]) {
+    static_assert(!(TT && LEAN), "the table form has no clamp-free variant");
     if constexpr (TT) m_tanh_vec_tab<W>(z, t, s_tanh_tab);
-    else m_tanh_vec<W>(z, t);
+    else m_tanh_vec<W, LEAN>(z, t);
 }
 
 // ---- the other activation functions `chain(widths, activations; output_activation)` can be built with
 // (src/neural-network.jl:42-58: any hidden activation, any output activation; the reference's scripts use tanh and
 // softplus, which the specialised paths of Mlp are written for).  Codes = cude_kernels.h kActHidden* / kActOut*.
 // hidden layer of W units; the derivative is always a function of the OUTPUT h (what the reverse sweep has at hand)
-template <int W, int HA, bool TT>
+template <int W, int HA, bool TT, bool LEAN = false>
 __device__ __forceinline__ void act_hidden_vec(const double (&z)[W], double (&h)[W]) {
+    static_assert(!LEAN || HA == kActHiddenTanh, "clamp-free form: tanh only");
     if constexpr (HA == kActHiddenTanh) {
-        act_tanh_vec<W, TT>(z, h);
+        act_tanh_vec<W, TT, LEAN>(z, h);
     } else if constexpr (HA == kActHiddenRelu) {
 #pragma unroll
         for (int j = 0; j < W; j++) h[j] = fmax(z[j], 0.0);
@@ -165,10 +168,10 @@ __device__ __forceinline__ double act_hidden_deriv(double h) {
     else return 1.0;
 }
 // output unit: value and derivative
-template <int OA, bool LONE>
+template <int OA, bool LONE, bool LEAN = false>
 __device__ __forceinline__ double act_out(double x, double* sig) {
     if constexpr (OA == kActOutSoftplus) {
-        return m_softplus_t<LONE>(x, sig);
+        return m_softplus_t<LONE, LEAN>(x, sig);
     } else {
         *sig = 1.0;
         return x;
@@ -177,12 +180,13 @@ __device__ __forceinline__ double act_out(double x, double* sig) {
 
 // softplus(x) = log(1+exp(x)) (reference form, evaluated stably); *sig receives the logistic derivative.
 // (LONE: no other exponential in the kernel -- networks with the table tanh; see m_exp2x_t)
-template <bool LONE>
-__device__ __forceinline__ double act_softplus(double x, double* sig) { return m_softplus_t<LONE>(x, sig); }
-template <bool LONE>
+// (LEAN: without the clamp of -0.5 |x| at -350 -- output units whose weights bound |x|, m_lean_bounds)
+template <bool LONE, bool LEAN = false>
+__device__ __forceinline__ double act_softplus(double x, double* sig) { return m_softplus_t<LONE, LEAN>(x, sig); }
+template <bool LONE, bool LEAN = false>
 __device__ __forceinline__ double act_softplus_val(double x) {
     double sig;
-    return m_softplus_t<LONE>(x, &sig);
+    return m_softplus_t<LONE, LEAN>(x, &sig);
 }
 
 // ------------------------------------------------------------------------------------ MLP
@@ -342,6 +346,15 @@ struct Mlp {
     // the gain is lost (+2.7 % at 1e6); for width 8 (351 VGPRs, one wave per SIMD, 25 KB of LDS per wave) the
     // exposed LDS latency makes it slower (+6 % / +18 %).  So the table is compiled in for widths 6 and 7 only.
     static constexpr bool HAS_TAB = (NV == 1 && W >= 6 && W <= 7) && !GENERAL;
+    // networks whose fixed-step c-peptide gradient kernel carries clamp-free sweeps beside the clamped ones (cpep_kernel,
+    // cude_cpep.hip): the exponential-form tanh shapes of widths 6 and 7 with a hidden layer above the first
+    static constexpr bool HAS_LEAN = HAS_TAB && !TT && D >= 2;
+    // m_lean_bounds of this shape: do the weights prove the clamps of the layers above the first and of the output unit dead?
+    __device__ static __forceinline__ bool lean_ok(cptr_t p) {
+        bool tanh_lean, out_lean;
+        m_lean_bounds(p, NIN, W, D, &tanh_lean, &out_lean);
+        return tanh_lean && out_lean;
+    }
     struct Exps {
         double v[W];
     };
@@ -358,10 +371,17 @@ struct Mlp {
         }
     }
     // A_j = exp(2 (W1[j,0] x + c_j))
+    // SAFE: without the +-340 clamps, for callers that reach here only behind a passed tab_safe (below) of the piece x
+    // lies in: the pre-activation at x sits between its values at the piece's two ends, which tab_safe holds within
+    // +-300, so the clamps return it bit for bit
+    template <bool SAFE = false>
     __device__ static __forceinline__ void tab_anchor(cptr_t p, const double (&c)[W], double x, Exps& A) {
         const SCol<W> col = ld_col<W>(p, 0);
 #pragma unroll
-        for (int j = 0; j < W; j++) A.v[j] = m_exp2x(fmin(fmax(fma(col.v[j], x, c[j]), -340.0), 340.0));
+        for (int j = 0; j < W; j++) {
+            const double z = fma(col.v[j], x, c[j]);
+            A.v[j] = m_exp2x(SAFE ? z : fmin(fmax(z, -340.0), 340.0));
+        }
     }
     // The recurrence is exact (every anchor, factor and product representable, nothing clamped) iff the
     // pre-activations stay within +-300 over the whole linear piece [x0, x0+dx] and move by at most 300 per step.
@@ -381,6 +401,9 @@ struct Mlp {
 
     // hidden activations of all layers: h[l][j]; returns the output pre-activation.
     // use_tab: the layer-1 activations come from the exponentials E1 instead of x.
+    // LEAN (here and in every evaluation below): the hidden layers above the first and the output unit run without their
+    // clamps (act_tanh_vec / act_softplus) -- for callers whose parameter set passed m_lean_bounds; layer 1 keeps its own
+    template <bool LEAN = false>
     __device__ static __forceinline__ double forward(cptr_t p, const double (&c)[W], const double (&x)[NV],
                                                      double (&h)[D][W], bool use_tab = false,
                                                      const Exps* E1 = nullptr) {
@@ -420,7 +443,7 @@ struct Mlp {
                         if (i0 + g < W) z[j] = fma(col.v[g * W + j], h[l - 1][i0 + g], z[j]);
             }
             CUDE_FENCE();
-            act_hidden_vec<W, HA, TT>(z, h[l]);
+            act_hidden_vec<W, HA, TT, LEAN>(z, h[l]);
         }
         CUDE_FENCE();
         const SCol<W> wo = ld_col<W>(p, OUT);
@@ -456,6 +479,7 @@ struct Mlp {
             v.w[q] = t;
         }
     }
+    template <bool LEAN = false>
     __device__ static __forceinline__ double eval_vw(cptr_t p, const VW& v, const double (&c)[W], const double (&x)[NV],
                                                      bool use_tab, const Exps* E1) {
         double h[W], z[W];
@@ -480,7 +504,7 @@ struct Mlp {
             for (int i = 0; i < W; i++)
 #pragma unroll
                 for (int j = 0; j < W; j++) z[j] = fma(v.w[o + W * i + j], h[i], z[j]);
-            act_tanh_vec<W, TT>(z, h);
+            act_tanh_vec<W, TT, LEAN>(z, h);
         }
         constexpr int oo = (D - 1) * LH;
         double z0 = v.w[oo + W], z1 = 0.0;
@@ -489,7 +513,7 @@ struct Mlp {
             if (i & 1) z1 = fma(v.w[oo + i], h[i], z1);
             else z0 = fma(v.w[oo + i], h[i], z0);
         }
-        return act_softplus_val<TT>(z0 + z1);
+        return act_softplus_val<TT, LEAN>(z0 + z1);
     }
 
     // ---- kept activations (c-peptide gradient kernel, CpepArgs::act): the forward sweep hands out the tanh outputs of
@@ -563,6 +587,7 @@ struct Mlp {
     }
 
     // value only
+    template <bool LEAN = false>
     __device__ static __forceinline__ double eval(cptr_t p, const double (&c)[W], const double (&x)[NV],
                                                   bool use_tab = false, const Exps* E1 = nullptr) {
         p = launder(p);
@@ -570,7 +595,7 @@ struct Mlp {
         // (the pipelined weight stream of eval_grad_pf does not pay here: measured +1 ... +7 % on the forward-only
         // kernels, which run at 3-4 waves per SIMD and lose a wave or spill SGPRs to the extra groups in flight)
         double sig;
-        return act_out<OA, TT>(forward(p, c, x, h, use_tab, E1), &sig);
+        return act_out<OA, TT, LEAN>(forward<LEAN>(p, c, x, h, use_tab, E1), &sig);
     }
 
     // ---- value + weighted reverse sweep with a SOFTWARE-PIPELINED weight stream.
@@ -603,7 +628,7 @@ struct Mlp {
     // forward half: hidden activations h, output pre-activation returned; wo and (KEEP) the last hidden layer's last
     // column group stay loaded for the backward half
     // SKIP_OUT: the output unit is not evaluated (its logistic derivative is supplied: eval_grad_pf with SIG_IN)
-    template <bool KEEP, bool SKIP_OUT = false>
+    template <bool KEEP, bool SKIP_OUT = false, bool LEAN = false>
     __device__ static __forceinline__ double forward_pf(cptr_t p, const double (&c)[W], const double (&x)[NV],
                                                         double (&h)[D][W], bool use_tab, const Exps* E1, SCol<W>& wo,
                                                         SCol<W * CGP>& glast) {
@@ -650,7 +675,7 @@ struct Mlp {
                     for (int j = 0; j < W; j++) z[j] = fma(grp[l][g].v[k * W + j], h[l - 1][g * CGP + k], z[j]);
             }
             CUDE_FENCE();
-            act_tanh_vec<W, TT>(z, h[l]);
+            act_tanh_vec<W, TT, LEAN>(z, h[l]);
         }
         CUDE_FENCE();
         // the last hidden layer's last column group is needed again right after the output unit
@@ -669,7 +694,7 @@ struct Mlp {
     // SIG_IN: the output unit's logistic derivative comes from the caller (kept by the forward sweep, CpepArgs::act);
     // neither the output pre-activation nor the softplus is evaluated (52 of ~375 instructions of a 2-6-6-1 reverse
     // evaluation) and the return value is 0
-    template <bool WANT_DX, class A, bool SIG_IN = false, bool PIN = kPinLayers, int DX0 = 0>
+    template <bool WANT_DX, class A, bool SIG_IN = false, bool PIN = kPinLayers, int DX0 = 0, bool LEAN = false>
     __device__ static __forceinline__ double eval_grad_pf(cptr_t p, const double (&c)[W], const double (&x)[NV],
                                                           double wgt, A& acc, double (&dx)[NV],
                                                           bool use_tab, const Exps* E1, double sig_in = 0.0) {
@@ -677,10 +702,10 @@ struct Mlp {
         double h[D][W];
         SCol<W * CGP> grp[D][NG];        // grp[l][g]: column group g of hidden layer l (l >= 1), backward order
         SCol<W> wo;
-        const double zo = forward_pf<true, SIG_IN>(p, c, x, h, use_tab, E1, wo, grp[D - 1][NG - 1]);
+        const double zo = forward_pf<true, SIG_IN, LEAN>(p, c, x, h, use_tab, E1, wo, grp[D - 1][NG - 1]);
         double sig = sig_in;
         double y = 0.0;
-        if (!SIG_IN) y = act_softplus<TT>(zo, &sig);
+        if (!SIG_IN) y = act_softplus<TT, LEAN>(zo, &sig);
         // ------------------------------------------------ backward (column groups from the last to the first)
         const double dz = wgt * sig;
         acc[G_OUT + W] += dz;
@@ -822,14 +847,20 @@ struct Mlp {
     }
     // m_tanh_vec for pre-activations that come out of rw_fma.  The compiler cannot see that an inline-asm result is
     // no signalling NaN and would put a canonicalising v_max in front of every clamp; the clamp min(|z|, 20) is
-    // therefore written as the instruction it compiles to elsewhere.
+    // therefore written as the instruction it compiles to elsewhere.  LEAN: no clamp (|z| itself is an operand modifier
+    // of the exponential's first instructions, not an instruction).
+    template <bool LEAN = false>
     __device__ static __forceinline__ void rw_tanh(const double (&z)[W], double (&t)[W]) {
         double d[W], pre[W];
 #pragma unroll
         for (int j = 0; j < W; j++) {
-            double a;
-            asm("v_min_f64 %0, |%1|, %2" : "=v"(a) : "v"(z[j]), "s"(20.0));
-            d[j] = m_exp2x(a) + 1.0;
+            if constexpr (LEAN) {
+                d[j] = m_exp2x(fabs(z[j])) + 1.0;
+            } else {
+                double a;
+                asm("v_min_f64 %0, |%1|, %2" : "=v"(a) : "v"(z[j]), "s"(20.0));
+                d[j] = m_exp2x(a) + 1.0;
+            }
         }
         pre[0] = d[0];
 #pragma unroll
@@ -844,7 +875,7 @@ struct Mlp {
         t[0] = copysign(fma(-2.0, r, 1.0), z[0]);
     }
     // The operations, their order and their operands are those of eval_grad_pf<false> for D = 2, NV = 1.
-    template <class A>
+    template <class A, bool LEAN = false>
     __device__ static __forceinline__ void eval_grad_rw(cptr_t p, const RW& r, const RS& rs, const double (&c)[W],
                                                         const double (&x)[NV], double wgt, A& acc, bool use_tab,
                                                         const Exps* E1) {
@@ -865,7 +896,7 @@ struct Mlp {
             z[j.value] = rw_fma<W * i.value + j.value>(r, h[0][i.value], z[j.value]);
         });
         CUDE_FENCE();
-        rw_tanh(z, h[1]);
+        rw_tanh<LEAN>(z, h[1]);
         CUDE_FENCE();
         double z0 = seed_from_sgpr(rs.bo), z1 = 0.0;
 #pragma unroll
@@ -874,7 +905,7 @@ struct Mlp {
             else z0 = fma(rs.wo.v[i], h[1][i], z0);
         }
         double sig;
-        act_softplus<TT>(z0 + z1, &sig);
+        act_softplus<TT, LEAN>(z0 + z1, &sig);
         const double dz = wgt * sig;
         acc[G_OUT + W] += dz;
         double dh[W], d[W];
@@ -912,18 +943,18 @@ struct Mlp {
     // kernels ask for it -- their evaluation sits inside a conditional of the replay loop and, unpinned, every
     // accumulator is copied to another register at the end of it: 32 v_mov_b64 per evaluation of a 2-4-4-1 network)
     // DX0: first input whose derivative is wanted (the suppression model's input 1 has no adjoint: cude_supp.hip)
-    template <bool WANT_DX, class A, bool PIN = kPinLayers, int DX0 = 0>
+    template <bool WANT_DX, class A, bool PIN = kPinLayers, int DX0 = 0, bool LEAN = false>
     __device__ static __forceinline__ double eval_grad(cptr_t p, const double (&c)[W], const double (&x)[NV],
                                                        double wgt, A& acc, double (&dx)[NV],
                                                        bool use_tab = false, const Exps* E1 = nullptr) {
 #ifndef CUDE_NO_PREFETCH
-        if constexpr (HAS_PF) return eval_grad_pf<WANT_DX, A, false, PIN, DX0>(p, c, x, wgt, acc, dx, use_tab, E1);
+        if constexpr (HAS_PF) return eval_grad_pf<WANT_DX, A, false, PIN, DX0, LEAN>(p, c, x, wgt, acc, dx, use_tab, E1);
 #endif
         p = launder(p);
         double h[D][W];
-        const double zo = forward(p, c, x, h, use_tab, E1);
+        const double zo = forward<LEAN>(p, c, x, h, use_tab, E1);
         double sig;
-        const double y = act_out<OA, TT>(zo, &sig);
+        const double y = act_out<OA, TT, LEAN>(zo, &sig);
         backward<WANT_DX, A, PIN, DX0>(p, x, h, sig, wgt, acc, dx);
         return y;
     }
@@ -1213,6 +1244,7 @@ struct MmProd {
     static constexpr int NC = 1, NCST = 1, P = 1;
     static constexpr int NACC = 2;                  // [d/dp0, d/dk]
     static constexpr bool HAS_TAB = false;          // one division per evaluation: nothing to tabulate
+    static constexpr bool HAS_LEAN = false;
     static constexpr bool HAS_VW = false;
     static constexpr bool HAS_VW_SMALL = false;
     static constexpr bool HAS_RW = false;

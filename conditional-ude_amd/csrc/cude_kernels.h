@@ -122,6 +122,11 @@ struct CpepArgs {
     int32_t* tape_n;         // [N] accepted steps per subject of parameter set 0 (forward and gradient launches), or nullptr
     int32_t team;            // adaptive mode, small launches: 0 = a step's five evaluations on five waves (cude_adaptive_team.hip)
                              // where that kernel applies, -1 = never (option "adaptive_team" = 0)
+    int32_t lean_clamp;      // fixed-step gradient kernel of the lean shapes (Mlp::HAS_LEAN; cpep_kernel, cude_cpep.hip): non-zero =
+                             // a wave whose own parameter set passes Mlp::lean_ok runs the sweeps without the clamps of the
+                             // layers above the first and of the output unit (the same bits); 0 = every wave runs the clamped
+                             // sweeps.  No value forces the clamp-free form past the kernel's test.  In the four bytes of padding
+                             // behind `team`, for unit_seed's reason: every other field keeps its offset.
     double* gen_acc;         // fallback kernel (cude_generic.hip), gradient: [n_sets][P][N] per-lane accumulators; its tape
                              // (CpepArgs::tape) is [n_sets][steps][2 + n_state][N] with steps = S, or tape_cap when S == 0
     const int32_t* perm;     // adaptive kernels: lane `gid` works on subject perm[gid] (nullptr = identity).  Lanes of a wave

@@ -133,7 +133,13 @@ CUDE_HD double m_exp2x(double x) { return m_exp2x_t<false>(x); }
 CUDE_HD double m_exp(double y) { return m_exp2x(0.5 * y); }
 
 // denominators exp(2|z|)+1 of tanh, clamped so that products of up to 8 of them stay finite
-CUDE_HD double m_tanh_den(double z) { return m_exp2x(fmin(fabs(z), 20.0)) + 1.0; }
+// LEAN: without the clamp, for callers that KNOW |z| < 20 (m_lean_bounds below): min(|z|, 20) then returns |z| bit for bit
+template <bool LEAN>
+CUDE_HD double m_tanh_den_t(double z) {
+    if constexpr (LEAN) return m_exp2x(fabs(z)) + 1.0;
+    else return m_exp2x(fmin(fabs(z), 20.0)) + 1.0;
+}
+CUDE_HD double m_tanh_den(double z) { return m_tanh_den_t<false>(z); }
 
 CUDE_HD double m_tanh(double x) {
     const double r = m_rcp(m_tanh_den(x));
@@ -230,12 +236,13 @@ CUDE_HD void m_tanh_vec_tab(const double (&z)[W], double (&t)[W], const double* 
 // t[j] = tanh(z[j]) for a whole layer with ONE reciprocal (prefix-product trick).
 // (A lock-step variant that interleaves the W Horner chains was measured 5 % slower: two waves per
 // SIMD already cover the FMA latency and the extra live registers cost more than they buy.)
-template <int W>
+// LEAN: clamp-free denominators (m_tanh_den_t) -- the same bits wherever every |z[j]| < 20
+template <int W, bool LEAN = false>
 CUDE_HD void m_tanh_vec(const double (&z)[W], double (&t)[W]) {
     static_assert(W <= 8, "batched reciprocal: product of denominators must stay below 1e308");
     double d[W], pre[W];
 #pragma unroll
-    for (int j = 0; j < W; j++) d[j] = m_tanh_den(z[j]);
+    for (int j = 0; j < W; j++) d[j] = m_tanh_den_t<LEAN>(z[j]);
     pre[0] = d[0];
 #pragma unroll
     for (int j = 1; j < W; j++) pre[j] = pre[j - 1] * d[j];
@@ -276,9 +283,13 @@ CUDE_HD void m_tanh_from_exp(const double (&E)[W], double (&t)[W]) {
 }
 
 // softplus value and logistic derivative (LONE: this is the kernel's only exponential, see m_exp2x_t)
-template <bool LONE>
+// LEAN: without the clamp at -350, for callers that KNOW |x| < 700 (m_lean_bounds below): max(-0.5 |x|, -350) then
+// returns -0.5 |x| bit for bit
+template <bool LONE, bool LEAN = false>
 CUDE_HD double m_softplus_t(double x, double* sig) {
-    const double e = m_exp2x_t<LONE>(fmax(-0.5 * fabs(x), -350.0));     // exp(-|x|) in (0, 1]
+    double xe = -0.5 * fabs(x);
+    if constexpr (!LEAN) xe = fmax(xe, -350.0);
+    const double e = m_exp2x_t<LONE>(xe);                        // exp(-|x|) in (0, 1]
     const double d = 1.0 + e;                                    // in (1, 2]
     // log(d) = 2 atanh(s), s = (v-1)/(v+1), v = d or d/2 so that v in [1/sqrt2, sqrt2]
     const bool big = d > 1.41421356237309504880;
@@ -322,6 +333,42 @@ CUDE_HD double m_softplus(double x, double* sig) { return m_softplus_t<false>(x,
 CUDE_HD double m_softplus_val(double x) {
     double sig;
     return m_softplus(x, &sig);
+}
+
+// ---- which clamps of a tanh / softplus network its weights prove dead.
+// Every hidden layer's outputs lie in [-1, 1] (the clamped layer-1 forms return 1 - 2/d with d >= 1 to a few ulp), so the
+// pre-activations of the layers above obey |z_j| <= |b_j| + sum_k |W_jk| and the output unit's |x| <= |b| + sum_j |w_j|,
+// whatever the inputs.  The computed pre-activation exceeds the exact sum by at most W + 1 roundings and the layer below
+// its range by a few ulp: the margins 19.5 < 20 and 690 < 700 (the clamp of -0.5 |x| at -350) cover both a million
+// times over.  Under the bounds min(|z|, 20) and max(-0.5 |x|, -350) return their first argument bit for bit, i.e. the
+// LEAN forms above are the clamped ones.  Parameter layout: SimpleChains, [vec_colmajor(W); b] per layer (cude_device.h
+// Mlp): nin inputs, d hidden layers of w units, one output unit.
+//   tanh_lean: every hidden layer ABOVE THE FIRST satisfies the first bound (vacuous for d = 1)
+//   out_lean:  the output unit satisfies the second
+// The comparisons are written so that a NaN (and an Inf) anywhere in the sums gives false.
+constexpr double kLeanTanhBound = 19.5;
+constexpr double kLeanOutBound = 690.0;
+template <class Ptr>
+CUDE_HD void m_lean_bounds(Ptr p, int nin, int w, int d, bool* tanh_lean, bool* out_lean) {
+    const int l1 = w * nin + w, lh = w * w + w;
+    bool ok = true;
+#pragma unroll
+    for (int l = 1; l < d; l++) {
+        const int o = l1 + (l - 1) * lh;
+#pragma unroll
+        for (int j = 0; j < w; j++) {
+            double s = fabs(p[o + w * w + j]);
+#pragma unroll
+            for (int k = 0; k < w; k++) s += fabs(p[o + w * k + j]);
+            ok &= (s <= kLeanTanhBound);
+        }
+    }
+    *tanh_lean = ok;
+    const int out = l1 + (d - 1) * lh;
+    double s = fabs(p[out + w]);
+#pragma unroll
+    for (int j = 0; j < w; j++) s += fabs(p[out + j]);
+    *out_lean = s <= kLeanOutBound;
 }
 
 }  // namespace cude
