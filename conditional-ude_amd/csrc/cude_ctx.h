@@ -1,6 +1,9 @@
 // Internal header of libcude_hip.so's host side: the context, its helpers and what the translation units share.
 //   cude_context.hip   contexts, populations, parameters, solver tables, run-time options
-//   cude_launch.hip    launch selection (one-lane / time-split / mixed), ensemble launches and every entry point built on them
+//   cude_select.hip    the measured rules that pick a launch shape (one-lane / time-split / mixed, sets per launch, depths)
+//   cude_launch.hip    the launches themselves (ensemble, parameter sets, tangent, dense output) and the entry points that are one
+//   cude_batch.hip     the entry points that batch such launches (simulate, bands, profiles, fits, scores, screening)
+//   cude_mh.hip        the Metropolis driver (cude_mh_estep, cude_mh_chain)
 //   cude_optimise.hip  Adam (single steps and captured runs), L-BFGS on host vectors
 //   cude_train.hip     restarts trained side by side with their optimiser state on the device (cude_train_restarts)
 //   cude_comm.hip      multi-GPU: RCCL (dlopen) and the peer-write exchange over IPC-mapped mailboxes
@@ -284,15 +287,73 @@ void interp_weights(double theta, double* w7);      // h-free dense-output weigh
 // suppression model, fixed step: state 1 at outputs (step[k], w[k][0..6]) relative to u1(t_0) (SuppArgs::obs_rho)
 void supp_output_rho(int S, double h, const std::vector<int32_t>& step, const std::vector<double>& w, std::vector<double>& obs_rho);
 int32_t apply_option(cude_ctx* c, const char* name, const char* value);
-// ---- cude_launch.hip
-cude::CpepArgs cpep_args(const cude_ctx* c);
-cude::SuppArgs supp_args(const cude_ctx* c);
+// plain one-dimensional copies on the context's stream, asynchronous, the byte count taken from the element type
+template <class T>
+hipError_t push(const cude_ctx* c, T* dst, const T* src, size_t n) {       // host -> device
+    return hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream);
+}
+template <class T>
+hipError_t fetch(const cude_ctx* c, T* dst, const T* src, size_t n) {      // device -> host; null dst: an output nobody asked for
+    return dst ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
+// A buffer cut into consecutive arrays.  The layout is written once, as a function of a Carve: run on a null base it
+// measures (take returns null, `used` is the size), run on the buffer it hands out the pointers -- carve() does both.
+template <class T>
+struct Carve {
+    T* base;
+    size_t used = 0;
+    T* take(size_t n) {
+        T* const p = base ? base + used : nullptr;
+        used += n;
+        return p;
+    }
+};
+template <class T, class Layout>
+hipError_t carve(DevBuf<T>& buf, Layout layout) {
+    Carve<T> size{nullptr};
+    layout(size);
+    const hipError_t e = buf.reserve(size.used);
+    if (e != hipSuccess) return e;
+    Carve<T> v{buf.p};
+    layout(v);
+    return hipSuccess;
+}
+
+// adaptive launches leave every subject's accepted-step count behind (of set 0 where there are several); tape_valid: the
+// launch was the gradient evaluation whose tape cude_adaptive_steps pairs those counts with
+inline void note_adaptive_launch(cude_ctx* c, bool tape_valid) {
+    if (!adaptive(c)) return;
+    c->have_counts = true;
+    c->have_tape = tape_valid;
+}
+
+// ---- cude_select.hip
 size_t supp_act_doubles(const cude_ctx* c);
 bool supp_keep_activations(const cude_ctx* c, int64_t n_sets);
 size_t cpep_act_doubles(const cude_ctx* c);
+int cpep_keep_mode(const cude_ctx* c);
 bool cpep_keep_activations(const cude_ctx* c);
-int32_t ensure_tape(cude_ctx* c);
+bool supp_steps_only(const cude_ctx* c);
 int32_t setup_chunks(cude_ctx* c);
+int forward_chunks(const cude_ctx* c);
+int prio_shift_for(const cude_ctx* c, int64_t blocks);
+int prio_clock_for(const cude_ctx* c);
+double sets_scratch_budget(cude_ctx* c);
+constexpr int64_t kNoGridCap = std::numeric_limits<int64_t>::max();
+int64_t sets_per_launch(int64_t n, int64_t grid_cap, double budget_bytes, double bytes_per_set, int option_cap = 0);
+int mh_spec_depth(const cude_ctx* c, int n_mc);
+int mh_spec_depth_one_launch(const cude_ctx* c, int n_mc);
+int mh_spec_depth_blend(const cude_ctx* c, int n_mc, bool split);
+int fit_spec_depth(const cude_ctx* c, bool fsplit);
+// ---- cude_launch.hip
+cude::CpepArgs cpep_args(const cude_ctx* c);
+cude::SuppArgs supp_args(const cude_ctx* c);
+cude::Cpep2Args chunk_args(cude_ctx* c, const cude::CpepArgs& base, bool all_blocks = false, bool forward_only = false);
+int generic_tape_rows(const cude_ctx* c);
+int64_t tape_doubles_per_set(const cude_ctx* c);
+int32_t ensure_tape(cude_ctx* c);
+int32_t timed_pair(cude_ctx* c, hipEvent_t* e0, hipEvent_t* e1);
 int32_t run_ensemble(cude_ctx* c, bool grad, double* traj_dev, bool local_only = false, const double* cond_ov = nullptr,
                      double* sse_ov = nullptr);
 int32_t finish_loss(cude_ctx* c, double* loss, double* g_nn_host);
@@ -305,8 +366,47 @@ struct SetsRows {
 };
 int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t stride_nn, const double* cond,
                          int64_t stride_cond, double* g_cond, double* out, const SetsRows* rows = nullptr);
-int64_t scores_chunk_sets(cude_ctx* c, int64_t n_sets);
-int64_t info_chunk_sets(cude_ctx* c, int64_t n_live, bool stage);
+hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, bool keep_tape);
+// A forward solve of n_sets parameter sets in one launch (set k: nn + k * stride_nn, cond + k * N; the set index is a grid
+// dimension): what the entry points that batch solves differ in.  The rest of the launch is forward_sets's.
+struct SetsForward {
+    const double* cond = nullptr;       // [n_sets][N]
+    const double* nn = nullptr;         // stride_nn = 0: one network for every set
+    int64_t stride_nn = 0;
+    int n_sets = 0;
+    double* sse = nullptr;              // [n_sets][N] per-subject SSE, or null
+    double* partials = nullptr;         // [n_sets][nblocks][P + 2] of a launch that is not split: [sum SSE, failures] in
+                                        // the last two columns (reserve_sets_forward)
+    bool split = false;                 // the time-split forward kernels (c-peptide models, fixed step, chunks > 1)
+    const cude::MhSpecArgs* resolve_in_scan = nullptr;      // split only: the scan launch resolves this speculative round
+};
+int32_t reserve_sets_forward(cude_ctx* c, int64_t max_sets, bool split, DevBuf<double>& own_part);
+int32_t forward_sets(cude_ctx* c, const SetsForward& s);
+// Dense output (cude_simulate, cude_predictive_bands).  The tables of ALL output times of a call, on the device: in
+// fixed-step mode the step every output falls into, its seven interpolation weights and, for the suppression model, state 1
+// there; in adaptive mode the times themselves (the kernel interpolates at them).  An entry depends on its own time
+// alone, so launches over a stretch of the times point into the tables.
+struct OutputTables {
+    DevBuf<int32_t> d_step;
+    DevBuf<double> d_w, d_rho, d_times;
+    int32_t upload(cude_ctx* c, int64_t n_times, const double* times);      // (queued; the host copies live as long as this)
+  private:
+    std::vector<int32_t> step;
+    std::vector<double> w, rho;
+};
+// One outputs-only launch: output times [k0, k0 + kn) of the tables, the states to `traj`.
+struct DenseLaunch {
+    const double* cond = nullptr;       // [N], or [n_sets][N]
+    int32_t n_sets = 0;                 // 0: one set (the launch's second grid dimension otherwise; one network for all)
+    int64_t set_stride = 0;             // set k writes traj + k * set_stride
+    int64_t k0 = 0, kn = 0;
+    double* traj = nullptr;             // c-peptide models: [n_state x kn x N] per set
+    int64_t traj_ss = 0, traj_st = 0, traj_sn = 0;      // suppression model: state s, output o, subject i at s ss + o st + i sn
+    double* partials = nullptr;
+    bool keep_perm = true;              // adaptive mode: false = the caller's order, not the re-grouped launch order
+    int64_t blk_first = 0, blk_count = 0;       // workgroups [blk_first, blk_first + blk_count) of the population (0: all)
+};
+int32_t launch_dense(cude_ctx* c, const OutputTables& tables, const DenseLaunch& d);
 // ---- cude_optimise.hip
 void drop_graph(cude_ctx* c);
 int32_t ensure_trace(cude_ctx* c, int64_t n);

@@ -363,6 +363,42 @@ def test_dense_output_matches_the_oracle_interpolant(arch, n_state):
     eng.close()
 
 
+@pytest.mark.parametrize("n_steps", [30, 0], ids=["fixed", "adaptive"])
+def test_dense_output_in_several_launches_gives_the_same_bits(n_steps):
+    """cude_simulate of a c-peptide model, 2-6-6-1, 70 subjects (two workgroups, the second partial), 23 output times with
+    t_0, the last data time and a repeated value: launches of 5 times each (option "dense_chunk") against one launch, and
+    single rows against a call at that one time -- an output depends on its own time alone.  Fixed step: 3 states.
+    Adaptive mode (which integrates the 2-state model alone: 3 states are refused at cude_create): in the caller's order
+    and after cude_adaptive_regroup, when the launch order is a permutation of it."""
+    from cude.engine import Engine
+    arch = (2, 6, 2)
+    c = make_cpep_case(70, arch)
+    n_state = 3 if n_steps else 2
+    eng = Engine("cpep", arch, n_steps=n_steps, n_state=n_state)
+    eng.set_population_cpep(c["tp"], c["G"], c["obs"], c["age"], c["t2dm"])
+    eng.set_params(c["nn"], c["beta"])
+    t0, t1 = float(c["tp"][0]), float(c["tp"][-1])
+    times = np.sort(np.concatenate([[t0, t1, 0.37 * (t0 + t1), 0.37 * (t0 + t1)], np.linspace(t0, t1, 21)[1:-1]]))
+    assert times.size == 23 and times[0] == t0 and times[-1] == t1 and np.any(np.diff(times) == 0.0)
+
+    def check():
+        eng.set_option("dense_chunk", 0)
+        whole = eng.simulate(times)
+        assert whole.shape == (n_state, 23, 70) and np.all(np.isfinite(whole))
+        for j in (0, 11, 22):
+            assert np.array_equal(whole[:, j], eng.simulate([times[j]])[:, 0]), j
+        eng.set_option("dense_chunk", 5)
+        assert np.array_equal(eng.simulate(times), whole)
+        return whole
+
+    whole = check()
+    if n_steps == 0:
+        eng.loss_grad()                                 # (the accepted-step counts the re-ordering goes by)
+        eng.adaptive_regroup()
+        assert np.array_equal(check(), whole)           # per-subject results do not depend on the launch order
+    eng.close()
+
+
 def test_size_limits_and_missing_values():
     """Edges of the domain: the maximum number of observation times (32) against the oracle, T = 33 and an empty
     population rejected with a status, a one-subject population, and missing values (NaN in a subject's glucose /
