@@ -448,7 +448,7 @@ struct StageRows<NS, true> {
 };
 
 constexpr int kUnrolledKnots = 5;                  // the reference's five sampling times (c-peptide/02-conditional.jl)
-// cude_adaptive_unrolled.hip: the c-peptide MLP shapes (cude_device.h CUDE_CPEP_SHAPES) and the symbolic model on grids of at most kUnrolledKnots times; hipErrorNotSupported
+// cude_adaptive_unrolled.hip: the c-peptide MLP shapes (cude_shapes.h CUDE_CPEP_SHAPES) and the symbolic model on grids of at most kUnrolledKnots times; hipErrorNotSupported
 // for any other shape (the caller then runs the phase-machine kernel)
 hipError_t launch_cpep_adaptive_unrolled(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s);
 // cude_adaptive_team.hip: the same solve with a step's five network evaluations on five waves, for launches of at most
@@ -460,8 +460,8 @@ hipError_t launch_cpep_adaptive_unrolled_part1(const NetShape& net, bool grad, c
 hipError_t launch_cpep_adaptive_unrolled_part2(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s);
 hipError_t launch_cpep_adaptive_part1(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s);
 hipError_t launch_cpep_adaptive_part2(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s);
-// cude_adaptive_unrolled_supp.hip: the suppression model, shapes of the reference's experiments
-#define CUDE_SUPP_AD_UNROLLED(X) X(3, 5) X(3, 3) X(3, 4) X(3, 2)
+// cude_adaptive_unrolled_supp.hip: the suppression model, shapes of the reference's experiments (cude_shapes.h
+// CUDE_SUPP_AD_UNROLLED)
 hipError_t launch_supp_adaptive_unrolled(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s);
 
 }  // namespace cude

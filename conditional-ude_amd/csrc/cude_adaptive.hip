@@ -64,32 +64,6 @@ static hipError_t launch_adaptive_out(const SuppArgs& a, hipStream_t s) {
 #define CUDE_AD_PART 0
 #endif
 #if CUDE_AD_PART == 0
-// the one-body kernel of the suppression shapes the unrolled kernel does not cover (cude_adaptive.h CUDE_SUPP_AD_UNROLLED
-// lists those it does; A/B builds with -DCUDE_ADAPT_ONE_BODY compile them here as well)
-#ifdef CUDE_ADAPT_ONE_BODY
-#define CUDE_SUPP_AD_SHAPES(X) CUDE_SUPP_SHAPES(X)
-#else
-#define CUDE_SUPP_AD_SHAPES(X) X(4, 2) X(6, 2) X(5, 2) X(8, 2) X(4, 3) X(4, 4) X(5, 3) X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
-#endif
-
-template <int NIN, int W, int D>
-static hipError_t launch_cpep_adaptive_general(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
-#define Y(HA, OA) \
-    if (net.hact == HA && net.oact == OA) return launch_adaptive<CpepAd<CpepNetG<NIN, W, D, HA, OA>>, true>(a, a.TG, grad, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-template <int W, int D>
-static hipError_t launch_supp_adaptive_general(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
-#define Y(HA, OA)                                                                                                        \
-    if (net.hact == HA && net.oact == OA)                                                                                \
-        return a.T_data > 0 ? launch_adaptive_out<SuppAdOut<W, D, HA, OA>>(a, s) : launch_adaptive<SuppAd<W, D, HA, OA>, false>(a, 0, grad, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_cpep_adaptive(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
     if (a.TG < 2 || a.TG > kMaxObs || a.T < 1) return hipErrorInvalidValue;
     if (grad && a.obs == nullptr) return hipErrorInvalidValue;
@@ -104,17 +78,14 @@ hipError_t launch_cpep_adaptive(const NetShape& net, bool grad, const CpepArgs& 
     if (net.symbolic())
         return a.cond_raw ? launch_adaptive<CpepAd<MmProd<true>>, true>(a, a.TG, grad, s)
                           : launch_adaptive<CpepAd<MmProd<false>>, true>(a, a.TG, grad, s);
-    if (net.general()) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_adaptive_general<NIN, W, D>(net, grad, a, s);
-        CUDE_CPEP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_adaptive<CpepAd<Mlp<NIN, W, D, 1>>, true>(a, a.TG, grad, s);
-    CUDE_CPEP_SHAPES_0(X)
-#undef X
-    hipError_t e = launch_cpep_adaptive_part1(net, grad, a, s);
+    if (net.general())
+        return visit_cpep_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_adaptive<CpepAd<CpepNetG<sh.nin, sh.width, sh.depth, act.hact, act.oact>>, true>(a, a.TG, grad, s);
+        });
+    hipError_t e = visit_cpep_shapes_0(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_adaptive<CpepAd<Mlp<sh.nin, sh.width, sh.depth, 1>>, true>(a, a.TG, grad, s);
+    });
+    if (e == hipErrorNotSupported) e = launch_cpep_adaptive_part1(net, grad, a, s);
     if (e == hipErrorNotSupported) e = launch_cpep_adaptive_part2(net, grad, a, s);
     return e == hipErrorNotSupported ? hipErrorInvalidValue : e;
 }
@@ -127,34 +98,28 @@ hipError_t launch_supp_adaptive(const NetShape& net, bool grad, const SuppArgs& 
         if (e != hipErrorNotSupported) return e;
     }
 #endif
-    if (net.general()) {
-#define X(W, D) if (net.width == W && net.depth == D) return launch_supp_adaptive_general<W, D>(net, grad, a, s);
-        CUDE_SUPP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(W, D)                                                                                                          \
-    if (net.width == W && net.depth == D)                                                                                \
-        return a.T_data > 0 ? launch_adaptive_out<SuppAdOut<W, D>>(a, s) : launch_adaptive<SuppAd<W, D>, false>(a, 0, grad, s);
-    CUDE_SUPP_AD_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_supp_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            constexpr int W = sh.width, D = sh.depth, HA = act.hact, OA = act.oact;
+            return a.T_data > 0 ? launch_adaptive_out<SuppAdOut<W, D, HA, OA>>(a, s) : launch_adaptive<SuppAd<W, D, HA, OA>, false>(a, 0, grad, s);
+        });
+    // (the one-body kernel of the shapes the unrolled kernel does not cover: cude_shapes.h CUDE_SUPP_AD_SHAPES)
+    return visit_supp_ad_shapes(net, hipErrorInvalidValue, [&](auto sh) {
+        return a.T_data > 0 ? launch_adaptive_out<SuppAdOut<sh.width, sh.depth>>(a, s)
+                            : launch_adaptive<SuppAd<sh.width, sh.depth>, false>(a, 0, grad, s);
+    });
 }
 #elif CUDE_AD_PART == 1
 hipError_t launch_cpep_adaptive_part1(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_adaptive<CpepAd<Mlp<NIN, W, D, 1>>, true>(a, a.TG, grad, s);
-    CUDE_CPEP_SHAPES_1(X)
-#undef X
-    return hipErrorNotSupported;
+    return visit_cpep_shapes_1(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_adaptive<CpepAd<Mlp<sh.nin, sh.width, sh.depth, 1>>, true>(a, a.TG, grad, s);
+    });
 }
 #else
 hipError_t launch_cpep_adaptive_part2(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_adaptive<CpepAd<Mlp<NIN, W, D, 1>>, true>(a, a.TG, grad, s);
-    CUDE_CPEP_SHAPES_2(X)
-#undef X
-    return hipErrorNotSupported;
+    return visit_cpep_shapes_2(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_adaptive<CpepAd<Mlp<sh.nin, sh.width, sh.depth, 1>>, true>(a, a.TG, grad, s);
+    });
 }
 #endif
 

@@ -415,11 +415,9 @@ hipError_t launch_cpep_adaptive_team(const NetShape& net, bool grad, const CpepA
     const int64_t waves1 = (grad ? (a.N + kBlock - 1) / kBlock : launch_blocks(a)) * (a.n_sets > 0 ? a.n_sets : 1);
     if (waves1 > kTeamMaxWaves) return hipErrorNotSupported;
     if (grad && a.obs == nullptr) return hipErrorInvalidValue;
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_team<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_SHAPES_0(X)
-#undef X
-    return hipErrorNotSupported;
+    return visit_cpep_shapes_0(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_team<CpepAd<Mlp<sh.nin, sh.width, sh.depth, 1>>>(a, grad, s);
+    });
 }
 
 }  // namespace cude

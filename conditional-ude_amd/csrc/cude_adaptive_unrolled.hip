@@ -351,28 +351,23 @@ hipError_t launch_cpep_adaptive_unrolled(const NetShape& net, bool grad, const C
     if (grad && a.obs == nullptr) return hipErrorInvalidValue;
     if (net.symbolic())
         return a.cond_raw ? launch_unrolled<CpepAd<MmProd<true>>>(a, grad, s) : launch_unrolled<CpepAd<MmProd<false>>>(a, grad, s);
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_unrolled<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_SHAPES_0(X)
-#undef X
-    const hipError_t e = launch_cpep_adaptive_unrolled_part1(net, grad, a, s);
+    hipError_t e = visit_cpep_shapes_0(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_unrolled<CpepAd<Mlp<sh.nin, sh.width, sh.depth, 1>>>(a, grad, s);
+    });
+    if (e == hipErrorNotSupported) e = launch_cpep_adaptive_unrolled_part1(net, grad, a, s);
     return e != hipErrorNotSupported ? e : launch_cpep_adaptive_unrolled_part2(net, grad, a, s);
 }
 #elif CUDE_AD_PART == 1
 hipError_t launch_cpep_adaptive_unrolled_part1(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_unrolled<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_SHAPES_1(X)
-#undef X
-    return hipErrorNotSupported;
+    return visit_cpep_shapes_1(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_unrolled<CpepAd<Mlp<sh.nin, sh.width, sh.depth, 1>>>(a, grad, s);
+    });
 }
 #else
 hipError_t launch_cpep_adaptive_unrolled_part2(const NetShape& net, bool grad, const CpepArgs& a, hipStream_t s) {
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_unrolled<CpepAd<Mlp<NIN, W, D, 1>>>(a, grad, s);
-    CUDE_CPEP_SHAPES_2(X)
-#undef X
-    return hipErrorNotSupported;
+    return visit_cpep_shapes_2(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_unrolled<CpepAd<Mlp<sh.nin, sh.width, sh.depth, 1>>>(a, grad, s);
+    });
 }
 #endif
 

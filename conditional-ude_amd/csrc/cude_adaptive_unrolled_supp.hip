@@ -367,12 +367,10 @@ static hipError_t launch_unrolled_supp_out(const SuppArgs& a, hipStream_t s) {
 
 hipError_t launch_supp_adaptive_unrolled(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
     if (net.general() || net.nin != 4 || a.T < 1) return hipErrorNotSupported;
-#define X(W, D)                                                                                                          \
-    if (net.width == W && net.depth == D)                                                                                \
-        return a.T_data > 0 ? launch_unrolled_supp_out<SuppAdOut<W, D>>(a, s) : launch_unrolled_supp<SuppAd<W, D>>(a, grad, s);
-    CUDE_SUPP_AD_UNROLLED(X)
-#undef X
-    return hipErrorNotSupported;
+    return visit_supp_ad_unrolled(net, hipErrorNotSupported, [&](auto sh) {
+        return a.T_data > 0 ? launch_unrolled_supp_out<SuppAdOut<sh.width, sh.depth>>(a, s)
+                            : launch_unrolled_supp<SuppAd<sh.width, sh.depth>>(a, grad, s);
+    });
 }
 
 }  // namespace cude

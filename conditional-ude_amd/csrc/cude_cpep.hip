@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((KEEP !=
 }
 
 // ------------------------------------------------------------------------------------ dispatch
-// (the shape lists: cude_device.h CUDE_CPEP_SHAPES / CUDE_CPEP_GENERAL_SHAPES)
+// (the shape lists and their visitors: cude_shapes.h)
 // shapes with a kept-activation variant of the gradient kernel: the forward sweep must already hold the upper layers'
 // weights in VGPRs (Mlp::HAS_VW) and there must be an upper layer to keep
 template <class Net>
@@ -125,49 +125,30 @@ static int grad_occupancy(int n_state, int T) {
                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cpep_kernel<Net, 2, true>, kBlock, lds);
     return e == hipSuccess ? n : 0;
 }
-template <int NIN, int W, int D>
-static hipError_t launch_general(const NetShape& net, int n_state, bool grad, const CpepArgs& a, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_shape<CpepNetG<NIN, W, D, HA, OA>>(n_state, grad, a, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-static bool general_shape(const NetShape& net) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return true;
-    CUDE_CPEP_GENERAL_SHAPES(X)
-#undef X
-    return false;
-}
 
 // resident waves per CU of the one-lane-per-subject gradient kernel (0 = unknown)
 int cpep_grad_waves_per_cu(const NetShape& net, int n_state, int T) {
     if (net.generic()) return 1;
     if (net.symbolic()) return grad_occupancy<MmProd<false>>(n_state, T);
     if (net.general()) return 4;             // (not tuned: the path selector only needs "at least one wave per SIMD")
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return grad_occupancy<CpepNet<NIN, W, D>>(n_state, T);
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return 0;
+    return visit_cpep_shapes(net, 0, [&](auto sh) { return grad_occupancy<CpepNet<sh.nin, sh.width, sh.depth>>(n_state, T); });
 }
 
 // kept values per evaluation of the gradient kernel's kept-activation variant (0: the shape has none)
 int cpep_keep_values(const NetShape& net) {
     if (net.symbolic() || net.general() || net.generic()) return 0;
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return cpep_can_keep<CpepNet<NIN, W, D>>() ? CpepNet<NIN, W, D>::NKEEP : 0;
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return 0;
+    return visit_cpep_shapes(net, 0, [](auto sh) {
+        using Net = CpepNet<sh.nin, sh.width, sh.depth>;
+        return cpep_can_keep<Net>() ? Net::NKEEP : 0;
+    });
 }
 
 bool cpep_shape_supported(const NetShape& net, int n_state) {
     if (net.generic()) return false;         // (the tuned kernels; the fallback kernel takes what they do not)
     if (n_state != 2 && n_state != 3) return false;
     if (net.symbolic()) return true;
-    if (net.general()) return general_shape(net) && general_acts_compiled(net.hact, net.oact);
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return true;
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return false;
+    if (net.general()) return visit_cpep_general(net, false, [](auto, auto) { return true; });
+    return visit_cpep_shapes(net, false, [](auto) { return true; });
 }
 
 hipError_t launch_cpep(const NetShape& net, int n_state, bool grad, const CpepArgs& a, hipStream_t s) {
@@ -175,17 +156,13 @@ hipError_t launch_cpep(const NetShape& net, int n_state, bool grad, const CpepAr
     if (a.S == 0) return n_state != 2 ? hipErrorInvalidValue : launch_cpep_adaptive(net, grad, a, s);
     if (net.symbolic())
         return a.cond_raw ? launch_shape<MmProd<true>>(n_state, grad, a, s) : launch_shape<MmProd<false>>(n_state, grad, a, s);
-    if (net.general()) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_general<NIN, W, D>(net, n_state, grad, a, s);
-        CUDE_CPEP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(NIN, W, D) \
-    if (net.nin == NIN && net.width == W && net.depth == D) return launch_shape<CpepNet<NIN, W, D>>(n_state, grad, a, s);
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_cpep_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_shape<CpepNetG<sh.nin, sh.width, sh.depth, act.hact, act.oact>>(n_state, grad, a, s);
+        });
+    return visit_cpep_shapes(net, hipErrorInvalidValue, [&](auto sh) {
+        return launch_shape<CpepNet<sh.nin, sh.width, sh.depth>>(n_state, grad, a, s);
+    });
 }
 
 }  // namespace cude

@@ -1022,10 +1022,7 @@ static hipError_t run_shape(int n_state, bool grad, const Cpep2Args& a, hipStrea
 bool cpep2_shape_supported(const NetShape& net, int n_state) {
     if (net.general() || net.generic()) return false;         // other activation functions / shapes: the one-lane kernels only
     if (n_state != 2 && n_state != 3) return false;
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return true;
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return false;
+    return visit_cpep_shapes(net, false, [](auto) { return true; });
 }
 
 // resident waves per CU of the reverse kernel (register / LDS limited): the slot count of the chunk-count selector
@@ -1038,10 +1035,7 @@ static int rev_occupancy() {
     return n;
 }
 int cpep2_rev_waves_per_cu(const NetShape& net) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return rev_occupancy<NIN, W, D>();
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return 0;
+    return visit_cpep_shapes(net, 0, [](auto sh) { return rev_occupancy<sh.nin, sh.width, sh.depth>(); });
 }
 
 // once per context, outside any stream capture: the eight-wave scan may ask for more than 64 KB of LDS
@@ -1065,10 +1059,7 @@ hipError_t launch_cpep2_adjmap(const Cpep2Args& a, double* adj_map, hipStream_t 
 }
 
 hipError_t launch_cpep2(const NetShape& net, int n_state, bool grad, const Cpep2Args& a, hipStream_t s) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return run_shape<NIN, W, D>(n_state, grad, a, s);
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    return visit_cpep_shapes(net, hipErrorInvalidValue, [&](auto sh) { return run_shape<sh.nin, sh.width, sh.depth>(n_state, grad, a, s); });
 }
 
 }  // namespace cude

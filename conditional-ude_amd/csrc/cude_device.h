@@ -14,6 +14,7 @@
 
 #include "cude_kernels.h"
 #include "cude_math.h"
+#include "cude_shapes.h"
 
 namespace cude {
 
@@ -1201,34 +1202,15 @@ using SuppNet = Mlp<4, W, D, 3, true, (CUDE_SUPP_LDS_BIAS != 0)>;
 #endif
 
 // Networks with other activation functions (Mlp::GENERAL): compiled for the shapes the reference's experiments use and
-// the combinations below -- hidden tanh | relu | sigmoid, output softplus | identity, (tanh, softplus) being the
-// specialised default.  Y(hidden, output)
-#define CUDE_GENERAL_ACTS(Y) Y(0, 1) Y(1, 0) Y(1, 1) Y(2, 0) Y(2, 1)
+// the activation pairs of cude_shapes.h CUDE_GENERAL_ACTS
 template <int NIN, int W, int D, int HA, int OA>
 using CpepNetG = Mlp<NIN, W, D, 1, false, false, HA, OA>;
 template <int W, int D, int HA, int OA>
 using SuppNetG = Mlp<4, W, D, 3, false, false, HA, OA>;
-inline bool general_acts_compiled(int hact, int oact) {
-#define Y(HA, OA) if (hact == HA && oact == OA) return true;
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return false;
-}
 
-// The network shapes the tuned kernels are compiled for: the ONE statement of each list, read by every dispatcher (a
-// shape is compiled for all launches of its model or for none).  Dispatchers test the shapes in the order listed.
-// c-peptide models, X(inputs, width, hidden layers) -- in three groups, because the longest translation units compile
-// one group each (cude_adaptive*.hip -DCUDE_AD_PART=k, cude_refine.hip -DCUDE_REFINE_PART=k)
-#define CUDE_CPEP_SHAPES_0(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2) X(2, 8, 2) X(2, 4, 3) X(2, 3, 2) X(2, 5, 2) X(2, 7, 2)
-#define CUDE_CPEP_SHAPES_1(X) X(3, 6, 2) X(2, 4, 1) X(2, 6, 1) X(2, 6, 3) X(2, 8, 1) X(2, 8, 3) X(3, 8, 2) X(2, 3, 1)
-#define CUDE_CPEP_SHAPES_2(X) X(2, 5, 1) X(2, 7, 1) X(2, 3, 3) X(2, 5, 3) X(2, 7, 3) X(3, 4, 1) X(3, 6, 1) X(3, 4, 3)
-#define CUDE_CPEP_SHAPES(X) CUDE_CPEP_SHAPES_0(X) CUDE_CPEP_SHAPES_1(X) CUDE_CPEP_SHAPES_2(X)
-// ... and those that are also compiled with the other activation functions (CUDE_GENERAL_ACTS)
-#define CUDE_CPEP_GENERAL_SHAPES(X) X(2, 4, 2) X(2, 6, 2) X(3, 4, 2)
-// suppression model, X(width, hidden layers); with the other activation functions: the shapes of the reference's
-// experiment (stage-input mode only)
-#define CUDE_SUPP_SHAPES(X) X(3, 5) X(3, 2) X(4, 2) X(6, 2) X(5, 2) X(3, 3) X(8, 2) X(3, 4) X(4, 3) X(4, 4) X(5, 3) X(6, 3) X(3, 1) X(4, 1) X(6, 1) X(8, 1)
-#define CUDE_SUPP_GENERAL_SHAPES(X) X(3, 5) X(3, 3)
+// The network shapes the tuned kernels are compiled for: cude_shapes.h holds each list once, with the visitor every
+// dispatcher reads it through (visit_cpep_shapes(net, not_found, [&](auto shape) { ... Mlp<shape.nin, shape.width,
+// shape.depth, 1> ... }) and its like) and the static_asserts that hold the lists to what the dispatchers assume.
 
 // ------------------------------------------------------------------------------------ analytic production
 // Drop-in for Mlp<2, W, D, 1> in the c-peptide kernel: the production term found by symbolic regression,

@@ -174,42 +174,30 @@ hipError_t launch_cpep_refine(const NetShape& net, int n_state, const CpepArgs& 
     if (net.symbolic())
         return a.cond_raw ? launch_cpep_fused<MmProd<true>>(n_state, a, k, r, s) : launch_cpep_fused<MmProd<false>>(n_state, a, k, r, s);
     if (net.general()) return launch_cpep_refine_part1(net, n_state, a, k, r, s);
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused<Mlp<NIN, W, D, 1>>(n_state, a, k, r, s);
-    CUDE_CPEP_SHAPES_0(X)
-#undef X
-    const hipError_t e = launch_cpep_refine_part1(net, n_state, a, k, r, s);
+    hipError_t e = visit_cpep_shapes_0(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s);
+    });
+    if (e == hipErrorNotSupported) e = launch_cpep_refine_part1(net, n_state, a, k, r, s);
     return e != hipErrorNotSupported ? e : launch_cpep_refine_part2(net, n_state, a, k, r, s);
 }
 
 #elif CUDE_REFINE_PART == 1
-template <int NIN, int W, int D>
-static hipError_t launch_cpep_fused_general(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_cpep_fused<CpepNetG<NIN, W, D, HA, OA>>(n_state, a, k, r, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 // hipErrorNotSupported = not in this group
 hipError_t launch_cpep_refine_part1(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
-    if (net.general()) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused_general<NIN, W, D>(net, n_state, a, k, r, s);
-        CUDE_CPEP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused<Mlp<NIN, W, D, 1>>(n_state, a, k, r, s);
-    CUDE_CPEP_SHAPES_1(X)
-#undef X
-    return hipErrorNotSupported;
+    if (net.general())
+        return visit_cpep_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_cpep_fused<CpepNetG<sh.nin, sh.width, sh.depth, act.hact, act.oact>>(n_state, a, k, r, s);
+        });
+    return visit_cpep_shapes_1(net, hipErrorNotSupported, [&](auto sh) {
+        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s);
+    });
 }
 
 #elif CUDE_REFINE_PART == 2
 hipError_t launch_cpep_refine_part2(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fused<Mlp<NIN, W, D, 1>>(n_state, a, k, r, s);
-    CUDE_CPEP_SHAPES_2(X)
-#undef X
-    return hipErrorInvalidValue;
+    return visit_cpep_shapes_2(net, hipErrorInvalidValue, [&](auto sh) {
+        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s);
+    });
 }
 
 #else
@@ -242,27 +230,14 @@ static hipError_t launch_supp_fused(const SuppArgs& a, const RefineCfg& k, const
     return hipGetLastError();
 }
 
-template <int W, int D>
-static hipError_t launch_supp_fused_general(const NetShape& net, const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_supp_fused<W, D, HA, OA>(a, k, r, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_supp_refine(const NetShape& net, const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
     if (net.nin != 4 || net.generic() || a.T < 1 || a.T_data > 0 || a.rho == nullptr || a.obs_rho == nullptr || a.S < 1)
         return hipErrorInvalidValue;
-    if (net.general()) {
-#define X(W, D) if (net.width == W && net.depth == D) return launch_supp_fused_general<W, D>(net, a, k, r, s);
-        CUDE_SUPP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(W, D) if (net.width == W && net.depth == D) return launch_supp_fused<W, D>(a, k, r, s);
-    CUDE_SUPP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_supp_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_supp_fused<sh.width, sh.depth, act.hact, act.oact>(a, k, r, s);
+        });
+    return visit_supp_shapes(net, hipErrorInvalidValue, [&](auto sh) { return launch_supp_fused<sh.width, sh.depth>(a, k, r, s); });
 }
 #endif
 

@@ -91,30 +91,19 @@ static hipError_t launch_cpep_fixed(int n_state, const CpepSensArgs& a, hipStrea
     return hipGetLastError();
 }
 
-template <int NIN, int W, int D>
-static hipError_t launch_cpep_fixed_general(const NetShape& net, int n_state, const CpepSensArgs& a, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_cpep_fixed<CpepNetG<NIN, W, D, HA, OA>>(n_state, a, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_cpep_sens(const NetShape& net, int n_state, const CpepSensArgs& a, hipStream_t s) {
     if (net.generic() || a.partials == nullptr || a.obs == nullptr || a.T < 1 || a.n_sets > 1) return hipErrorInvalidValue;
     if (a.S == 0) return n_state == 2 ? launch_cpep_sens_adaptive(net, a, s) : hipErrorInvalidValue;
     if (n_state != 2 && n_state != 3) return hipErrorInvalidValue;
     if (net.symbolic())
         return a.cond_raw ? launch_cpep_fixed<MmProd<true>>(n_state, a, s) : launch_cpep_fixed<MmProd<false>>(n_state, a, s);
-    if (net.general()) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fixed_general<NIN, W, D>(net, n_state, a, s);
-        CUDE_CPEP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_fixed<Mlp<NIN, W, D, 1>>(n_state, a, s);
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_cpep_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_cpep_fixed<CpepNetG<sh.nin, sh.width, sh.depth, act.hact, act.oact>>(n_state, a, s);
+        });
+    return visit_cpep_shapes(net, hipErrorInvalidValue, [&](auto sh) {
+        return launch_cpep_fixed<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, s);
+    });
 }
 
 hipError_t launch_supp_sens(const NetShape& net, const SuppSensArgs& a, hipStream_t s) {
@@ -133,27 +122,14 @@ static hipError_t launch_cpep_tan(const CpepSensArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int NIN, int W, int D>
-static hipError_t launch_cpep_tan_general(const NetShape& net, const CpepSensArgs& a, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_cpep_tan<CpepNetG<NIN, W, D, HA, OA>>(a, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_cpep_sens_adaptive(const NetShape& net, const CpepSensArgs& a, hipStream_t s) {
     if (a.TG < 2 || a.TG > kMaxObs) return hipErrorInvalidValue;
     if (net.symbolic()) return a.cond_raw ? launch_cpep_tan<MmProd<true>>(a, s) : launch_cpep_tan<MmProd<false>>(a, s);
-    if (net.general()) {
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_tan_general<NIN, W, D>(net, a, s);
-        CUDE_CPEP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(NIN, W, D) if (net.nin == NIN && net.width == W && net.depth == D) return launch_cpep_tan<Mlp<NIN, W, D, 1>>(a, s);
-    CUDE_CPEP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_cpep_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_cpep_tan<CpepNetG<sh.nin, sh.width, sh.depth, act.hact, act.oact>>(a, s);
+        });
+    return visit_cpep_shapes(net, hipErrorInvalidValue, [&](auto sh) { return launch_cpep_tan<Mlp<sh.nin, sh.width, sh.depth, 1>>(a, s); });
 }
 
 #elif CUDE_SENS_PART == 2
@@ -192,26 +168,13 @@ static hipError_t launch_supp_fixed(const SuppSensArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int W, int D>
-static hipError_t launch_supp_fixed_general(const NetShape& net, const SuppSensArgs& a, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_supp_fixed<W, D, HA, OA>(a, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_supp_sens_fixed(const NetShape& net, const SuppSensArgs& a, hipStream_t s) {
     if (a.rho == nullptr || a.obs_rho == nullptr || a.S < 1) return hipErrorInvalidValue;
-    if (net.general()) {
-#define X(W, D) if (net.width == W && net.depth == D) return launch_supp_fixed_general<W, D>(net, a, s);
-        CUDE_SUPP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(W, D) if (net.width == W && net.depth == D) return launch_supp_fixed<W, D>(a, s);
-    CUDE_SUPP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_supp_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_supp_fixed<sh.width, sh.depth, act.hact, act.oact>(a, s);
+        });
+    return visit_supp_shapes(net, hipErrorInvalidValue, [&](auto sh) { return launch_supp_fixed<sh.width, sh.depth>(a, s); });
 }
 
 #else
@@ -224,25 +187,12 @@ static hipError_t launch_supp_tan(const SuppSensArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int W, int D>
-static hipError_t launch_supp_tan_general(const NetShape& net, const SuppSensArgs& a, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_supp_tan<SuppAdTan<W, D, HA, OA>>(a, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_supp_sens_adaptive(const NetShape& net, const SuppSensArgs& a, hipStream_t s) {
-    if (net.general()) {
-#define X(W, D) if (net.width == W && net.depth == D) return launch_supp_tan_general<W, D>(net, a, s);
-        CUDE_SUPP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(W, D) if (net.width == W && net.depth == D) return launch_supp_tan<SuppAdTan<W, D>>(a, s);
-    CUDE_SUPP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_supp_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_supp_tan<SuppAdTan<sh.width, sh.depth, act.hact, act.oact>>(a, s);
+        });
+    return visit_supp_shapes(net, hipErrorInvalidValue, [&](auto sh) { return launch_supp_tan<SuppAdTan<sh.width, sh.depth>>(a, s); });
 }
 #endif
 

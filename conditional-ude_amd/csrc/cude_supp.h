@@ -4,7 +4,7 @@
 
 namespace cude {
 
-// HA / OA: activation functions other than tanh / softplus (cude_device.h CUDE_GENERAL_ACTS) select the general network
+// HA / OA: activation functions other than tanh / softplus (cude_shapes.h CUDE_GENERAL_ACTS) select the general network
 template <int W, int D, int HA, int OA>
 struct SuppNetSel { using type = SuppNetG<W, D, HA, OA>; };
 template <int W, int D>

@@ -490,16 +490,6 @@ static hipError_t launch_one(const SuppArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int W, int D>
-static hipError_t launch_general(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
-#define Y(HA, OA)                                                                                 \
-    if (net.hact == HA && net.oact == OA)                                                         \
-        return grad ? launch_one<W, D, true, false, false, HA, OA>(a, s) : launch_one<W, D, false, false, false, HA, OA>(a, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 // resident waves per CU of the gradient kernel (stage-input mode; 0 = unknown): what the launch actually gets
 template <int W, int D>
 static int supp_grad_occupancy() {
@@ -512,25 +502,13 @@ static int supp_grad_occupancy() {
 int supp_grad_waves_per_cu(const NetShape& net) {
     if (net.generic()) return 1;
     if (net.general()) return 4;
-#define X(W, D) if (net.width == W && net.depth == D) return supp_grad_occupancy<W, D>();
-    CUDE_SUPP_SHAPES(X)
-#undef X
-    return 0;
+    return visit_supp_shapes(net, 0, [](auto sh) { return supp_grad_occupancy<sh.width, sh.depth>(); });
 }
 
 bool supp_shape_supported(const NetShape& net) {
     if (net.nin != 4 || net.generic()) return false;
-    if (net.general()) {
-        if (!general_acts_compiled(net.hact, net.oact)) return false;
-#define X(W, D) if (net.width == W && net.depth == D) return true;
-        CUDE_SUPP_GENERAL_SHAPES(X)
-#undef X
-        return false;
-    }
-#define X(W, D) if (net.width == W && net.depth == D) return true;
-    CUDE_SUPP_SHAPES(X)
-#undef X
-    return false;
+    if (net.general()) return visit_supp_general(net, false, [](auto, auto) { return true; });
+    return visit_supp_shapes(net, false, [](auto) { return true; });
 }
 
 hipError_t launch_supp(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s) {
@@ -540,19 +518,17 @@ hipError_t launch_supp(const NetShape& net, bool grad, const SuppArgs& a, hipStr
     if (a.T_data > 0) return grad ? hipErrorInvalidValue : launch_supp_dense(net, a, s);     // cude_supp_dense.hip
     if (net.general()) {
         if (a.ckpt_steps_only || a.act != nullptr) return hipErrorInvalidValue;
-#define X(W, D) if (net.width == W && net.depth == D) return launch_general<W, D>(net, grad, a, s);
-        CUDE_SUPP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
+        return visit_supp_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            constexpr int W = sh.width, D = sh.depth, HA = act.hact, OA = act.oact;
+            return grad ? launch_one<W, D, true, false, false, HA, OA>(a, s) : launch_one<W, D, false, false, false, HA, OA>(a, s);
+        });
     }
-#define X(W, D)                                                                                   \
-    if (net.width == W && net.depth == D)                                                         \
-        return !grad ? launch_one<W, D, false, false>(a, s)                                       \
-                     : (a.ckpt_steps_only ? launch_one<W, D, true, false, true>(a, s)             \
+    return visit_supp_shapes(net, hipErrorInvalidValue, [&](auto sh) {
+        constexpr int W = sh.width, D = sh.depth;
+        return !grad ? launch_one<W, D, false, false>(a, s)
+                     : (a.ckpt_steps_only ? launch_one<W, D, true, false, true>(a, s)
                         : (a.act != nullptr ? launch_one<W, D, true, true>(a, s) : launch_one<W, D, true, false>(a, s)));
-    CUDE_SUPP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    });
 }
 
 }  // namespace cude

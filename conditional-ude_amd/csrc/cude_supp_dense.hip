@@ -130,26 +130,13 @@ static hipError_t launch_dense(const SuppArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int W, int D>
-static hipError_t launch_dense_general(const NetShape& net, const SuppArgs& a, hipStream_t s) {
-#define Y(HA, OA) if (net.hact == HA && net.oact == OA) return launch_dense<W, D, HA, OA>(a, s);
-    CUDE_GENERAL_ACTS(Y)
-#undef Y
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_supp_dense(const NetShape& net, const SuppArgs& a, hipStream_t s) {
     if (net.nin != 4 || net.generic() || a.T_data < 1) return hipErrorInvalidValue;
-    if (net.general()) {
-#define X(W, D) if (net.width == W && net.depth == D) return launch_dense_general<W, D>(net, a, s);
-        CUDE_SUPP_GENERAL_SHAPES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(W, D) if (net.width == W && net.depth == D) return launch_dense<W, D>(a, s);
-    CUDE_SUPP_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    if (net.general())
+        return visit_supp_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
+            return launch_dense<sh.width, sh.depth, act.hact, act.oact>(a, s);
+        });
+    return visit_supp_shapes(net, hipErrorInvalidValue, [&](auto sh) { return launch_dense<sh.width, sh.depth>(a, s); });
 }
 
 // the lane-contiguous dense output [T][3][N] into the caller's [N][T][3]: 32 x 32 tiles of the [3T][N] matrix through LDS

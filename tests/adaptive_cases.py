@@ -38,19 +38,19 @@ import numpy as np
 
 import cude_oracle as o
 
-# csrc/cude_device.h CUDE_CPEP_SHAPES_0 / _1 / _2 and CUDE_SUPP_SHAPES, in their order
+# csrc/cude_shapes.h CUDE_CPEP_SHAPES_0 / _1 / _2 and CUDE_SUPP_SHAPES, in their order
 CPEP_SHAPES = [(2, 4, 2), (2, 6, 2), (3, 4, 2), (2, 8, 2), (2, 4, 3), (2, 3, 2), (2, 5, 2), (2, 7, 2),
                (3, 6, 2), (2, 4, 1), (2, 6, 1), (2, 6, 3), (2, 8, 1), (2, 8, 3), (3, 8, 2), (2, 3, 1),
                (2, 5, 1), (2, 7, 1), (2, 3, 3), (2, 5, 3), (2, 7, 3), (3, 4, 1), (3, 6, 1), (3, 4, 3)]
 SUPP_SHAPES = [(3, 5), (3, 2), (4, 2), (6, 2), (5, 2), (3, 3), (8, 2), (3, 4), (4, 3), (4, 4), (5, 3), (6, 3), (3, 1), (4, 1),
                (6, 1), (8, 1)]
 TEAM_SHAPES = CPEP_SHAPES[:8]                           # CUDE_CPEP_SHAPES_0
-SUPP_UNROLLED = [(3, 5), (3, 3), (3, 4), (3, 2)]        # csrc/cude_adaptive.h CUDE_SUPP_AD_UNROLLED
+SUPP_UNROLLED = [(3, 5), (3, 3), (3, 4), (3, 2)]        # csrc/cude_shapes.h CUDE_SUPP_AD_UNROLLED
 TWO_WORKGROUPS = [(2, 4, 2), (3, 6, 2), (2, 5, 1)]      # first shape of each group: run with 70 subjects (a second
                                                         # workgroup, a wave of six lanes), the others with 16
 SUPP_TWO_WORKGROUPS = [(3, 5), (4, 3), (3, 1)]          # the same for the tangent and fit kernels of the suppression model
                                                         # (tests/test_gpu_tangent_shapes.py): 70 subjects, the others 12
-# csrc/cude_device.h CUDE_CPEP_GENERAL_SHAPES / CUDE_SUPP_GENERAL_SHAPES: the shapes that are also compiled with the
+# csrc/cude_shapes.h CUDE_CPEP_GENERAL_SHAPES / CUDE_SUPP_GENERAL_SHAPES: the shapes that are also compiled with the
 # activation pairs of CUDE_GENERAL_ACTS, here as (hidden, output) names in its order (csrc/cude_kernels.h kActHidden* /
 # kActOut*: hidden 0 tanh, 1 relu, 2 sigmoid; output 0 softplus, 1 identity)
 CPEP_GENERAL_SHAPES = [(2, 4, 2), (2, 6, 2), (3, 4, 2)]

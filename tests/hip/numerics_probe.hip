@@ -231,7 +231,7 @@ hipError_t run_param_check(const double* p, int n_sets, double* out) {
     return hipSuccess;
 }
 
-// the networks the product kernels are compiled for (csrc/cude_device.h CUDE_CPEP_SHAPES, CUDE_SUPP_SHAPES;
+// the networks the product kernels are compiled for (csrc/cude_shapes.h CUDE_CPEP_SHAPES, CUDE_SUPP_SHAPES;
 // CUDE_CPEP_GENERAL_SHAPES / CUDE_SUPP_GENERAL_SHAPES x CUDE_GENERAL_ACTS, one shape per pair)
 enum Family { kCpep = 0, kSupp = 1, kCpepG = 2, kSuppG = 3 };
 

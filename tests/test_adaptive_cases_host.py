@@ -24,12 +24,12 @@ def _macro(header, name):
 
 
 def test_shape_lists_restate_the_headers():
-    groups = [_macro("cude_device.h", f"CUDE_CPEP_SHAPES_{q}") for q in range(3)]
+    groups = [_macro("cude_shapes.h", f"CUDE_CPEP_SHAPES_{q}") for q in range(3)]
     assert [len(g) for g in groups] == [8, 8, 8]
     assert ac.CPEP_SHAPES == groups[0] + groups[1] + groups[2] and ac.TEAM_SHAPES == groups[0]
     assert ac.TWO_WORKGROUPS == [g[0] for g in groups]
-    assert ac.SUPP_SHAPES == _macro("cude_device.h", "CUDE_SUPP_SHAPES")
-    assert ac.SUPP_UNROLLED == _macro("cude_adaptive.h", "CUDE_SUPP_AD_UNROLLED")
+    assert ac.SUPP_SHAPES == _macro("cude_shapes.h", "CUDE_SUPP_SHAPES")
+    assert ac.SUPP_UNROLLED == _macro("cude_shapes.h", "CUDE_SUPP_AD_UNROLLED")
     assert set(ac.SUPP_UNROLLED) <= set(ac.SUPP_SHAPES)
     with open(os.path.join(CSRC, "cude_adaptive.h")) as f:
         assert re.search(r"kUnrolledKnots = (\d+);", f.read()).group(1) == "5"
@@ -38,10 +38,10 @@ def test_shape_lists_restate_the_headers():
 
 def test_general_lists_restate_the_headers():
     """The lists tests/test_gpu_tangent_shapes.py walks for the other activation functions, and its 70-subject cases."""
-    assert ac.CPEP_GENERAL_SHAPES == _macro("cude_device.h", "CUDE_CPEP_GENERAL_SHAPES")
-    assert ac.SUPP_GENERAL_SHAPES == _macro("cude_device.h", "CUDE_SUPP_GENERAL_SHAPES")
+    assert ac.CPEP_GENERAL_SHAPES == _macro("cude_shapes.h", "CUDE_CPEP_GENERAL_SHAPES")
+    assert ac.SUPP_GENERAL_SHAPES == _macro("cude_shapes.h", "CUDE_SUPP_GENERAL_SHAPES")
     assert set(ac.CPEP_GENERAL_SHAPES) <= set(ac.CPEP_SHAPES) and set(ac.SUPP_GENERAL_SHAPES) <= set(ac.SUPP_SHAPES)
-    with open(os.path.join(CSRC, "cude_device.h")) as f:
+    with open(os.path.join(CSRC, "cude_shapes.h")) as f:
         pairs = re.search(r"^#define CUDE_GENERAL_ACTS\(Y\)(.*)$", f.read(), re.M).group(1)
     pairs = [tuple(int(v) for v in t.split(",")) for t in re.findall(r"Y\(([0-9, ]+)\)", pairs)]
     with open(os.path.join(CSRC, "cude_kernels.h")) as f:

@@ -3,13 +3,16 @@ data's own): the reference's figure script simulates its fitted model on range(0
 (suppression/figures.jl:66-74 through simul, suppression/src/suppression_model.jl:107-115: u0 from the data, the
 problem's time span, saveat = the given times).  Checked against the oracle's fixed-step and adaptive solves at the same
 output times, against cude_forward's trajectory at the data times (the same solve), on every kernel family the model can
-land on (tuned fixed-step, adaptive unrolled, adaptive one-body, fallback network), and through api.simul."""
+land on (tuned fixed-step, adaptive unrolled, adaptive one-body, fallback network), through api.simul, and -- at the
+data's own times, against cude_forward's trajectory -- for every network shape and activation pair the dense-output
+kernels are compiled for."""
 import os
 
 import numpy as np
 import pytest
 import torch  # noqa: F401  (first: shared HIP runtime)
 
+import adaptive_cases as ac
 from conftest import make_supp_case
 
 pytestmark = pytest.mark.gpu
@@ -42,9 +45,12 @@ def _oracle_chunked(fn, times, u0, k=28):
     return out
 
 
-def _engine(arch, tp, data, nn, theta, n_steps):
+def _engine(arch, tp, data, nn, theta, n_steps, acts=()):
     from cude.engine import Engine
     eng = Engine("supp", arch, n_steps=n_steps)
+    if acts:
+        eng.set_option("hidden_activation", acts[0])
+        eng.set_option("output_activation", acts[1])
     eng.set_population_supp(tp, data)
     eng.set_params(nn, theta)
     return eng
@@ -108,6 +114,38 @@ def test_adaptive_matches_the_oracle_and_keeps_the_steps(arch):
     eng.set_option("dense_layout", 0)
     assert np.array_equal(eng.simulate(dense), got)
     eng.close()
+
+
+def _data_times_against_forward(shape, n_steps, acts=()):
+    """simulate() at the data's own times is cude_forward's solve: the same bits with a fixed step (the property
+    test_fixed_step_tuned_kernel_matches_the_oracle holds 4-3x5-1 to), within 1e-12 in adaptive mode (the bar of
+    test_adaptive_matches_the_oracle_and_keeps_the_steps: saveat does not change the steps taken).  12 subjects, the
+    inputs of tests/test_gpu_adaptive_shapes.py (live biases; tests/test_adaptive_cases_host.py shows them adequate)."""
+    s = ac.supp_case(shape, ac.SUPP_SHAPES.index(shape), 12)
+    eng = _engine(s["arch"], s["tp"], s["data"], s["nn"], s["theta"], n_steps, acts)
+    assert not eng.fallback_kernel
+    got = eng.simulate(s["tp"])
+    fwd = eng.forward(want_traj=True)["traj"]
+    eng.close()
+    assert got.shape == fwd.shape == (3, len(s["tp"]), 12) and np.all(np.isfinite(fwd))
+    print(f"{s['arch']} {'-'.join(acts)} n_steps {n_steps}: max |simulate - forward| {np.max(np.abs(got - fwd)):.3e}")
+    if n_steps:
+        assert np.array_equal(got, fwd)
+    else:
+        assert np.max(np.abs(got - fwd)) <= 1e-12
+
+
+@pytest.mark.parametrize("n_steps", [30, 0], ids=["fixed", "adaptive"])
+@pytest.mark.parametrize("shape", ac.SUPP_SHAPES, ids=str)
+def test_every_compiled_shape_at_the_data_times(shape, n_steps):
+    """launch_supp_dense and the dense-output leg of launch_supp_adaptive (unrolled and one-body), all 16 shapes"""
+    _data_times_against_forward(shape, n_steps)
+
+
+@pytest.mark.parametrize("acts", ac.GENERAL_ACTS, ids=["-".join(a) for a in ac.GENERAL_ACTS])
+@pytest.mark.parametrize("shape", ac.SUPP_GENERAL_SHAPES, ids=str)
+def test_every_compiled_activation_pair_at_the_data_times(shape, acts):
+    _data_times_against_forward(shape, 30, acts)
 
 
 @pytest.mark.parametrize("n_steps", [20, 0], ids=["fixed", "adaptive"])
