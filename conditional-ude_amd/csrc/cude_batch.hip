@@ -42,6 +42,133 @@ int32_t check_output_times(const cude_ctx* c, int32_t n_times, const double* tim
 }
 }  // namespace
 
+
+// The device half of cude_network_information (rules 2 ... 7 there): the unit-seed launches and the fold, finish and cross
+// kernels.  Leaves b, d, jc, qf and status (tb.ia), A (tb.gn, with want_a) and the Schur complement (tb.schur, with
+// want_schur) on the device, in scratch of the context that the next call of this function reuses; writes rq.jac_out chunk
+// by chunk; tb.failed is final after the next synchronisation of the stream.  The caller has checked the arguments.
+int32_t cude::api::info_pass(cude_ctx* c, const InfoRequest& rq, InfoTables& tb) {
+    int32_t rc = CUDE_OK;
+    const int P = c->P;
+    const int64_t N = c->N;
+    const double* const cond = rq.cond;
+    const double* const cov = rq.cov;
+    double* const jac_out = rq.jac_out;
+    const int profiled = rq.profiled ? 1 : 0;
+    const bool cpep = is_cpep(c);
+    const int T = c->T, n_out = cpep ? T : 3 * T;
+    const int n_live = cpep ? T - 1 : 2 * (T - 1);
+    const bool want_a = rq.want_a, want_q = rq.want_q;
+    const int64_t chunk = n_live > 0 ? info_chunk_sets(c, n_live, jac_out != nullptr) : 1;
+    const bool single = chunk >= n_live;
+    const int span_max = cpep ? (int)chunk : 3 * (((int)chunk + 1) / 2) + 2;
+    const size_t n_part = cude::info_cross_partials(N, P);
+    // per-set rows of a launch: conditionals, SSEs, conditional gradients
+    HIP_TRY(c->sc_rows.reserve((size_t)chunk * P * N));
+    HIP_TRY(c->sc_sets.reserve((size_t)chunk * 3 * N));
+    HIP_TRY(c->ms_out.reserve((size_t)chunk * (P + 2)));
+    if (jac_out) HIP_TRY(c->ni_stage.reserve((size_t)N * span_max * P));
+    double* const d_cond = c->sc_sets.p;
+    double* const d_sse = d_cond + chunk * N;
+    double* const d_gcond = d_sse + chunk * N;
+    cude::InfoArgs& ia = tb.ia;
+    ia = cude::InfoArgs{};
+    ia.N = N; ia.P = P; ia.n_out = n_out; ia.supp = cpep ? 0 : 1;
+    for (int s = 0; s < 3; s++) ia.w[s] = cpep ? 1.0 : 1.0 / (c->scale[s] * c->scale[s]);
+    ia.pw = rq.pw;
+    // state (b, t, d are cleared as one stretch, jc and qf as another; the kernels take status at bad + N)
+    double *d_coup = nullptr, *d_cond0 = nullptr, *d_gn = nullptr, *d_x = nullptr, *d_schur = nullptr, *d_cov = nullptr,
+           *d_part = nullptr, *d_partx = nullptr;
+    int32_t* d_nfail = nullptr;
+    HIP_TRY(carve(c->ni_state, [&](Carve<double>& v) {
+        ia.b = v.take((size_t)P * N);           // [P][N]
+        ia.t = v.take((size_t)P * N);
+        ia.d = v.take(N);
+        ia.jc = v.take((size_t)n_out * N);      // [N][n_out]
+        ia.qf = v.take((size_t)n_out * N);
+        d_coup = v.take((size_t)P * N);         // the coupling table as [N][P]
+        d_cond0 = v.take(N);                    // the conditional vector
+        d_gn = v.take((size_t)P * P);           // gn, the Schur term, schur, cov: [P][P]
+        d_x = v.take((size_t)P * P);
+        d_schur = v.take((size_t)P * P);
+        d_cov = v.take((size_t)P * P);
+        d_part = v.take(n_part);                // two sets of cross-product partials
+        d_partx = v.take(n_part);
+    }));
+    HIP_TRY(carve(c->sc_int, [&](Carve<int32_t>& v) {
+        ia.bad = v.take(N);
+        ia.status = v.take(N);
+        d_nfail = v.take(1);
+    }));
+    ia.mask = c->param_mask.p;
+    const double* cond0 = c->cond.p;
+    if (cond) {
+        HIP_TRY(push(c, d_cond0, cond, N));
+        cond0 = d_cond0;
+    }
+    HIP_TRY(cude::launch_info_replicate(N, (int)chunk, cond0, d_cond, c->stream));
+    if (want_q) HIP_TRY(push(c, d_cov, cov, (size_t)P * P));
+    // the rows of t_0 and of suppression state 0 depend on no parameter: +0.0 without a launch
+    HIP_TRY(hipMemsetAsync(ia.jc, 0, (size_t)2 * n_out * N * sizeof(double), c->stream));
+    if (jac_out) std::memset(jac_out, 0, (size_t)N * n_out * P * sizeof(double));
+    SetsRows rows{c->sc_rows.p, d_sse, 0};
+    const auto solve = [&](int l0, int kn) {
+        rows.unit_seed = 1 + l0;
+        return eval_sets_device(c, kn, c->nn.p, 0, d_cond, N, d_gcond, c->ms_out.p, &rows);
+    };
+    if (n_live == 0) {       // (a population with one time point: the fold of nothing)
+        HIP_TRY(hipMemsetAsync(ia.b, 0, (size_t)(2 * P + 1) * N * sizeof(double), c->stream));
+        HIP_TRY(hipMemsetAsync(ia.bad, 0, (size_t)N * sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(d_part, 0, n_part * sizeof(double), c->stream));
+    }
+    // ---- first pass: b, d, the failures; the caller's Jacobian chunk by chunk.  With several chunks A is summed along in
+    // the hope that no subject fails (the second pass needs every launch again)
+    const bool a_along = want_a && !single && !want_q;
+    for (int l0 = 0; l0 < n_live; l0 += (int)chunk) {
+        const int kn = (int)std::min<int64_t>(chunk, n_live - l0);
+        if ((rc = solve(l0, kn))) return rc;
+        HIP_TRY(cude::launch_info_fold(ia, kn, l0, l0 == 0, c->sc_rows.p, d_gcond, d_sse, c->stream));
+        if (a_along) HIP_TRY(cude::launch_info_cross(ia, kn, l0, l0 == 0, c->sc_rows.p, nullptr, d_part, c->stream));
+        if (jac_out) {
+            const int o0 = ia.out_index(l0), span = ia.out_index(l0 + kn - 1) - o0 + 1;
+            HIP_TRY(hipMemsetAsync(c->ni_stage.p, 0, (size_t)N * span * P * sizeof(double), c->stream));
+            HIP_TRY(cude::launch_info_transpose(ia, kn, l0, span, c->sc_rows.p, true, c->ni_stage.p, c->stream));
+            HIP_TRY(hipMemcpy2DAsync(jac_out + (size_t)o0 * P, (size_t)n_out * P * sizeof(double), c->ni_stage.p,
+                                     (size_t)span * P * sizeof(double), (size_t)span * P * sizeof(double), (size_t)N,
+                                     hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipMemsetAsync(d_nfail, 0, sizeof(int32_t), c->stream));
+    HIP_TRY(cude::launch_info_finish(ia, d_nfail, c->stream));
+    int32_t& failed = tb.failed;
+    failed = 0;
+    HIP_TRY(fetch(c, &failed, d_nfail, 1));
+    // ---- second pass: A over the subjects that did not fail, and the quadratic forms (they need b and d complete).  One
+    // chunk: its rows are still there.  Several: the launches run again -- for the quadratic forms always, for A only where
+    // a subject failed, which the host has to ask the device about
+    bool again = want_q || (want_a && single);
+    if (a_along) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        again = failed > 0;
+    }
+    if (again) {
+        for (int l0 = 0; l0 < n_live; l0 += (int)chunk) {
+            const int kn = (int)std::min<int64_t>(chunk, n_live - l0);
+            if (!single && (rc = solve(l0, kn))) return rc;
+            if (want_a) HIP_TRY(cude::launch_info_cross(ia, kn, l0, l0 == 0, c->sc_rows.p, ia.status, d_part, c->stream));
+            if (want_q) HIP_TRY(cude::launch_info_qform(ia, kn, l0, profiled != 0, c->sc_rows.p, d_gcond, d_cov, c->stream));
+        }
+    }
+    if (want_a) HIP_TRY(cude::launch_info_cross_finish(ia, d_part, d_gn, c->stream));
+    if (rq.want_schur) {
+        HIP_TRY(cude::launch_info_cross(ia, 1, -1, true, ia.t, ia.status, d_partx, c->stream));
+        HIP_TRY(cude::launch_info_cross_finish(ia, d_partx, d_x, c->stream));
+        HIP_TRY(cude::launch_info_schur(P, d_gn, d_x, d_schur, c->stream));
+    }
+    tb.gn = d_gn; tb.schur = d_schur; tb.coup = d_coup; tb.nfail = d_nfail;
+    return CUDE_OK;
+}
+
 extern "C" {
 
 int32_t cude_simulate(cude_ctx* c, int32_t n_times, const double* times, double* traj) {
@@ -405,114 +532,15 @@ int32_t cude_network_information(cude_ctx* c, const double* cond, double penalty
     if (cov && qform_out)
         for (int64_t j = 0; j < (int64_t)P * P; j++)
             if (!std::isfinite(cov[j])) return fail(CUDE_ERR_ARG, "cov must be finite");
-    const bool cpep = is_cpep(c);
-    const int T = c->T, n_out = cpep ? T : 3 * T;
-    const int n_live = cpep ? T - 1 : 2 * (T - 1);
-    const bool want_a = gn_out || schur_out, want_q = qform_out != nullptr;
-    const int64_t chunk = n_live > 0 ? info_chunk_sets(c, n_live, jac_out != nullptr) : 1;
-    const bool single = chunk >= n_live;
-    const int span_max = cpep ? (int)chunk : 3 * (((int)chunk + 1) / 2) + 2;
-    const size_t n_part = cude::info_cross_partials(N, P);
-    // per-set rows of a launch: conditionals, SSEs, conditional gradients
-    HIP_TRY(c->sc_rows.reserve((size_t)chunk * P * N));
-    HIP_TRY(c->sc_sets.reserve((size_t)chunk * 3 * N));
-    HIP_TRY(c->ms_out.reserve((size_t)chunk * (P + 2)));
-    if (jac_out) HIP_TRY(c->ni_stage.reserve((size_t)N * span_max * P));
-    double* const d_cond = c->sc_sets.p;
-    double* const d_sse = d_cond + chunk * N;
-    double* const d_gcond = d_sse + chunk * N;
-    cude::InfoArgs ia{};
-    ia.N = N; ia.P = P; ia.n_out = n_out; ia.supp = cpep ? 0 : 1;
-    for (int s = 0; s < 3; s++) ia.w[s] = cpep ? 1.0 : 1.0 / (c->scale[s] * c->scale[s]);
-    ia.pw = penalty_weight;
-    // state (b, t, d are cleared as one stretch, jc and qf as another; the kernels take status at bad + N)
-    double *d_coup = nullptr, *d_cond0 = nullptr, *d_gn = nullptr, *d_x = nullptr, *d_schur = nullptr, *d_cov = nullptr,
-           *d_part = nullptr, *d_partx = nullptr;
-    int32_t* d_nfail = nullptr;
-    HIP_TRY(carve(c->ni_state, [&](Carve<double>& v) {
-        ia.b = v.take((size_t)P * N);           // [P][N]
-        ia.t = v.take((size_t)P * N);
-        ia.d = v.take(N);
-        ia.jc = v.take((size_t)n_out * N);      // [N][n_out]
-        ia.qf = v.take((size_t)n_out * N);
-        d_coup = v.take((size_t)P * N);         // the coupling table as [N][P]
-        d_cond0 = v.take(N);                    // the conditional vector
-        d_gn = v.take((size_t)P * P);           // gn, the Schur term, schur, cov: [P][P]
-        d_x = v.take((size_t)P * P);
-        d_schur = v.take((size_t)P * P);
-        d_cov = v.take((size_t)P * P);
-        d_part = v.take(n_part);                // two sets of cross-product partials
-        d_partx = v.take(n_part);
-    }));
-    HIP_TRY(carve(c->sc_int, [&](Carve<int32_t>& v) {
-        ia.bad = v.take(N);
-        ia.status = v.take(N);
-        d_nfail = v.take(1);
-    }));
-    ia.mask = c->param_mask.p;
-    const double* cond0 = c->cond.p;
-    if (cond) {
-        HIP_TRY(push(c, d_cond0, cond, N));
-        cond0 = d_cond0;
-    }
-    HIP_TRY(cude::launch_info_replicate(N, (int)chunk, cond0, d_cond, c->stream));
-    if (want_q) HIP_TRY(push(c, d_cov, cov, (size_t)P * P));
-    // the rows of t_0 and of suppression state 0 depend on no parameter: +0.0 without a launch
-    HIP_TRY(hipMemsetAsync(ia.jc, 0, (size_t)2 * n_out * N * sizeof(double), c->stream));
-    if (jac_out) std::memset(jac_out, 0, (size_t)N * n_out * P * sizeof(double));
-    SetsRows rows{c->sc_rows.p, d_sse, 0};
-    const auto solve = [&](int l0, int kn) {
-        rows.unit_seed = 1 + l0;
-        return eval_sets_device(c, kn, c->nn.p, 0, d_cond, N, d_gcond, c->ms_out.p, &rows);
-    };
-    if (n_live == 0) {       // (a population with one time point: the fold of nothing)
-        HIP_TRY(hipMemsetAsync(ia.b, 0, (size_t)(2 * P + 1) * N * sizeof(double), c->stream));
-        HIP_TRY(hipMemsetAsync(ia.bad, 0, (size_t)N * sizeof(int32_t), c->stream));
-        HIP_TRY(hipMemsetAsync(d_part, 0, n_part * sizeof(double), c->stream));
-    }
-    // ---- first pass: b, d, the failures; the caller's Jacobian chunk by chunk.  With several chunks A is summed along in
-    // the hope that no subject fails (the second pass needs every launch again)
-    const bool a_along = want_a && !single && !want_q;
-    for (int l0 = 0; l0 < n_live; l0 += (int)chunk) {
-        const int kn = (int)std::min<int64_t>(chunk, n_live - l0);
-        if ((rc = solve(l0, kn))) return rc;
-        HIP_TRY(cude::launch_info_fold(ia, kn, l0, l0 == 0, c->sc_rows.p, d_gcond, d_sse, c->stream));
-        if (a_along) HIP_TRY(cude::launch_info_cross(ia, kn, l0, l0 == 0, c->sc_rows.p, nullptr, d_part, c->stream));
-        if (jac_out) {
-            const int o0 = ia.out_index(l0), span = ia.out_index(l0 + kn - 1) - o0 + 1;
-            HIP_TRY(hipMemsetAsync(c->ni_stage.p, 0, (size_t)N * span * P * sizeof(double), c->stream));
-            HIP_TRY(cude::launch_info_transpose(ia, kn, l0, span, c->sc_rows.p, true, c->ni_stage.p, c->stream));
-            HIP_TRY(hipMemcpy2DAsync(jac_out + (size_t)o0 * P, (size_t)n_out * P * sizeof(double), c->ni_stage.p,
-                                     (size_t)span * P * sizeof(double), (size_t)span * P * sizeof(double), (size_t)N,
-                                     hipMemcpyDeviceToHost, c->stream));
-        }
-    }
-    HIP_TRY(hipMemsetAsync(d_nfail, 0, sizeof(int32_t), c->stream));
-    HIP_TRY(cude::launch_info_finish(ia, d_nfail, c->stream));
-    int32_t failed = 0;
-    HIP_TRY(fetch(c, &failed, d_nfail, 1));
-    // ---- second pass: A over the subjects that did not fail, and the quadratic forms (they need b and d complete).  One
-    // chunk: its rows are still there.  Several: the launches run again -- for the quadratic forms always, for A only where
-    // a subject failed, which the host has to ask the device about
-    bool again = want_q || (want_a && single);
-    if (a_along) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        again = failed > 0;
-    }
-    if (again) {
-        for (int l0 = 0; l0 < n_live; l0 += (int)chunk) {
-            const int kn = (int)std::min<int64_t>(chunk, n_live - l0);
-            if (!single && (rc = solve(l0, kn))) return rc;
-            if (want_a) HIP_TRY(cude::launch_info_cross(ia, kn, l0, l0 == 0, c->sc_rows.p, ia.status, d_part, c->stream));
-            if (want_q) HIP_TRY(cude::launch_info_qform(ia, kn, l0, profiled != 0, c->sc_rows.p, d_gcond, d_cov, c->stream));
-        }
-    }
-    if (want_a) HIP_TRY(cude::launch_info_cross_finish(ia, d_part, d_gn, c->stream));
-    if (schur_out) {
-        HIP_TRY(cude::launch_info_cross(ia, 1, -1, true, ia.t, ia.status, d_partx, c->stream));
-        HIP_TRY(cude::launch_info_cross_finish(ia, d_partx, d_x, c->stream));
-        HIP_TRY(cude::launch_info_schur(P, d_gn, d_x, d_schur, c->stream));
-    }
+    InfoRequest rq;
+    rq.cond = cond; rq.pw = penalty_weight; rq.cov = cov; rq.profiled = profiled != 0; rq.jac_out = jac_out;
+    rq.want_a = gn_out || schur_out; rq.want_schur = schur_out != nullptr; rq.want_q = qform_out != nullptr;
+    InfoTables tb;
+    if ((rc = info_pass(c, rq, tb))) return rc;
+    const cude::InfoArgs& ia = tb.ia;
+    const int n_out = ia.n_out;
+    double *const d_coup = tb.coup, *const d_gn = tb.gn, *const d_schur = tb.schur;
+    int32_t& failed = tb.failed;
     if (coupling_out) {
         HIP_TRY(cude::launch_info_transpose(ia, 1, -1, 1, ia.b, false, d_coup, c->stream));
         HIP_TRY(fetch(c, coupling_out, d_coup, (size_t)P * N));

@@ -6,6 +6,7 @@
 //   cude_mh.hip        the Metropolis driver (cude_mh_estep, cude_mh_chain)
 //   cude_optimise.hip  Adam (single steps and captured runs), L-BFGS on host vectors
 //   cude_train.hip     restarts trained side by side with their optimiser state on the device (cude_train_restarts)
+//   cude_lm.hip        Levenberg-Marquardt on the information matrices (cude_lm_candidates, cude_train_lm) and its kernels
 //   cude_comm.hip      multi-GPU: RCCL (dlopen) and the peer-write exchange over IPC-mapped mailboxes
 #pragma once
 #include <dlfcn.h>
@@ -253,6 +254,8 @@ struct cude_ctx {
     cude::api::DevBuf<int32_t> sc_int;                                 // ... cross-product partials; kept between calls
     cude::api::DevBuf<double> ni_state, ni_stage;                      // cude_network_information: fold state and matrices, the
                                                                        // staging of a chunk's rows as [N][outputs][P]
+    cude::api::DevBuf<double> lm_buf, lm_part;                         // cude_lm_candidates / cude_train_lm: the damped steps'
+    cude::api::DevBuf<int32_t> lm_int;                                 // ... tables and trial sets, the trial launch's partials
     double scratch_budget = 0.0;       // bytes of scratch one multi-set launch may use (sets_scratch_budget)
     // cude_train_restarts (cude_train.hip): the restarts' optimiser state, resident between iterations
     cude::api::DevBuf<double> tr_m_nn, tr_v_nn, tr_m_cond, tr_v_cond, tr_trace;     // Adam moments [K][P] / [K][N], loss trace
@@ -407,6 +410,23 @@ struct DenseLaunch {
     int64_t blk_first = 0, blk_count = 0;       // workgroups [blk_first, blk_first + blk_count) of the population (0: all)
 };
 int32_t launch_dense(cude_ctx* c, const OutputTables& tables, const DenseLaunch& d);
+// ---- cude_batch.hip
+// The device half of cude_network_information, shared with the Levenberg-Marquardt entry points (cude_lm.hip).
+struct InfoRequest {
+    const double* cond = nullptr;       // host [N]; null: the context's conditionals
+    double pw = 0.0;
+    const double* cov = nullptr;        // host [P][P], with want_q
+    bool profiled = false;
+    double* jac_out = nullptr;          // host [N][n_out][P], written chunk by chunk
+    bool want_a = false, want_schur = false, want_q = false;
+};
+struct InfoTables {
+    cude::InfoArgs ia;                  // b [P][N], d [N], jc, qf [N][n_out], status [N] on the device
+    double *gn = nullptr, *schur = nullptr, *coup = nullptr;    // [P][P], [P][P], staging of the coupling table as [N][P]
+    int32_t* nfail = nullptr;           // device: failed subjects
+    int32_t failed = 0;                 // its host copy: final after the next synchronisation of the stream
+};
+int32_t info_pass(cude_ctx* c, const InfoRequest& rq, InfoTables& tb);
 // ---- cude_optimise.hip
 void drop_graph(cude_ctx* c);
 int32_t ensure_trace(cude_ctx* c, int64_t n);

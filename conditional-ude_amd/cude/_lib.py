@@ -15,6 +15,7 @@ MODEL_SUPP = 1
 MODEL_CPEP_SYM = 2
 COND_LOG = 0
 COND_RAW = 1
+LM_GRAD, LM_DECREASE, LM_STALLED, LM_MAX_ITERS, LM_FAILED = range(5)      # cude_train_lm's status (CUDE_LM_*)
 UNIQUE_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 128
 
@@ -87,6 +88,10 @@ _SIGNATURES = {
     "cude_network_information": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cude_n_outputs": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "cude_lm_candidates": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "cude_train_lm": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                  C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cude_mh_chain": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "cude_n_failed": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),

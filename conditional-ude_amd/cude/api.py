@@ -621,6 +621,35 @@ def _adam_then_lbfgs(eng, nn0, cond0, adam_iters, lbfgs_iters, lr, callback=None
     return res["x"][:P], res["x"][P:], res["f"]
 
 
+LM_STATUS = ("grad", "decrease", "stalled", "max_iters", "failed")      # cude_train_lm's status codes 0 ... 4, by name
+
+
+def _second_stage(second_stage):
+    if second_stage not in ("lbfgs", "lm"):
+        raise ValueError('second_stage must be "lbfgs" or "lm"')
+    return second_stage == "lm"
+
+
+def _adam_then_lm(eng, nn0, cond0, adam_iters, lm_iters, lr, trace=None):
+    """The Adam stage of _adam_then_lbfgs, then Levenberg-Marquardt on the expected-information matrices (cude_train_lm) in
+    place of L-BFGS; it ends at a relative decrease of 1e-10 or after lm_iters iterations."""
+    eng.set_params(nn0, cond0)
+    if adam_iters > 0:
+        eng.adam_init(lr)
+        losses = eng.adam_run(adam_iters)
+        if not np.all(np.isfinite(losses)):
+            raise FloatingPointError("solver failure (non-finite loss) during Adam")
+        if trace is not None:
+            trace.extend(float(v) for v in losses)
+    res = eng.train_lm(max_iters=lm_iters, ftol=1e-10)
+    if LM_STATUS[res["status"]] == "failed":
+        raise FloatingPointError("solver failure (non-finite loss or a failed subject) during Levenberg-Marquardt")
+    if trace is not None:
+        trace.extend(float(v) for v in res["trace"])
+    nn, cond = eng.get_params()
+    return nn, cond, float(res["trace"][-1])
+
+
 def _batched_adam_then_lbfgs(eng, nn_inits, cond_inits, adam_iters, lbfgs_iters, lr, traces=None, native=True):
     """The K selected restarts trained SIDE BY SIDE instead of one after the other (the reference's loop,
     src/parameter-estimation.jl:372-383 / suppression_model.jl:140-170): every optimiser iteration evaluates the K
@@ -672,7 +701,8 @@ def _batched_adam_then_lbfgs(eng, nn_inits, cond_inits, adam_iters, lbfgs_iters,
 def train(models, timepoints, cpeptide_data, rng_or_nn, *, initial_guesses=None, selected_initials=None,
           lhs_lower_bound=-2.0, lhs_upper_bound=0.0, n_conditional_parameters=1, number_of_iterations_adam=1000,
           number_of_iterations_lbfgs=1000, learning_rate_adam=1e-2, initial_beta=-2.0, lbfgs_lower_bound=-4.0,
-          lbfgs_upper_bound=1.0, lbfgs_iterations=1000, n_steps=None, side_by_side=True, method="search"):
+          lbfgs_upper_bound=1.0, lbfgs_iterations=1000, n_steps=None, side_by_side=True, method="search",
+          second_stage="lbfgs"):
     """Three methods of the reference, selected by the types of the 1st and 4th argument as Julia's dispatch does:
     * a single CPeptideUDEModel + rng: the conventional UDE on one (mean) subject (:205-247): `initial_guesses`
       (default 10 000) initialisations screened by their loss, the best `selected_initials` (10) -> Adam -> L-BFGS.
@@ -681,7 +711,10 @@ def train(models, timepoints, cpeptide_data, rng_or_nn, *, initial_guesses=None,
       restarts are trained side by side (one launch per optimiser iteration for all of them) unless
       side_by_side=False.
     * array of network parameters: per-subject estimation of the conditional parameter with the network
-      frozen (:272-288); `method` as estimate_conditional."""
+      frozen (:272-288); `method` as estimate_conditional.
+    second_stage="lm" (population training only): every selected restart runs its Adam iterations, then train_lm's
+    Levenberg-Marquardt loop (at most number_of_iterations_lbfgs iterations) in place of L-BFGS, one restart after the other."""
+    lm = _second_stage(second_stage)
     if isinstance(models, CPeptideUDEModel):
         return _train_ude(models, timepoints, cpeptide_data, rng_or_nn,
                           initial_guesses=10_000 if initial_guesses is None else initial_guesses,
@@ -707,7 +740,7 @@ def train(models, timepoints, cpeptide_data, rng_or_nn, *, initial_guesses=None,
         nn_inits = dict(zip(order, nn_sel))
         ode_inits = _Columns(dict(zip(order, cond_sel)))
         sols = []
-        if side_by_side and len(order) > 1:
+        if side_by_side and len(order) > 1 and not lm:
             fits = _batched_adam_then_lbfgs(eng, nn_sel, cond_sel,
                                             number_of_iterations_adam, number_of_iterations_lbfgs, learning_rate_adam)
             for fit in fits:
@@ -721,8 +754,9 @@ def train(models, timepoints, cpeptide_data, rng_or_nn, *, initial_guesses=None,
             return sols
         for k in order:
             try:
-                nn, cond, obj = _adam_then_lbfgs(eng, nn_inits[k], ode_inits[:, k], number_of_iterations_adam,
-                                                 number_of_iterations_lbfgs, learning_rate_adam)
+                nn, cond, obj = (_adam_then_lm if lm else _adam_then_lbfgs)(
+                    eng, nn_inits[k], ode_inits[:, k], number_of_iterations_adam, number_of_iterations_lbfgs,
+                    learning_rate_adam)
                 sols.append(OptimizationSolution(
                     u=ComponentArray(neural=nn, conditional=np.repeat(cond[:, None], n_conditional_parameters, 1)),
                     objective=obj))
@@ -1138,16 +1172,18 @@ def suppression_predictive(p, theta_samples, prob, individual_data, timepoints, 
 
 
 def fit_suppression_model(p_init, prob, data, timepoints, lam, *, select_best_n=1, adam_iters=2000, lbfgs_iters=2000,
-                          n_steps=None, side_by_side=True):
+                          n_steps=None, side_by_side=True, second_stage="lbfgs"):
     """fit_suppression_model (:132-177): screen all initials, keep the best n, Adam() [eta = 1e-3] then L-BFGS.
     The kept restarts are trained side by side (one launch per optimiser iteration for all of them) unless
-    side_by_side=False."""
+    side_by_side=False.  second_stage="lm": train_lm's Levenberg-Marquardt loop (at most lbfgs_iters iterations) in place
+    of L-BFGS, one restart after the other."""
+    lm = _second_stage(second_stage)
     pop = _supp_population(prob, data, timepoints, lam, n_steps)
     eng = pop.engine
     init_losses = eng.multistart_forward(np.stack([p.neural for p in p_init]), np.stack([p.theta for p in p_init]))
     best = np.argsort(init_losses, kind="stable")[:max(1, select_best_n)]
     sols, traces = [], []
-    if side_by_side and len(best) > 1:
+    if side_by_side and len(best) > 1 and not lm:
         traces = [[] for _ in best]
         fits = _batched_adam_then_lbfgs(eng, np.stack([p_init[k].neural for k in best]),
                                         np.stack([p_init[k].theta for k in best]), adam_iters, lbfgs_iters, 1e-3,
@@ -1162,8 +1198,11 @@ def fit_suppression_model(p_init, prob, data, timepoints, lam, *, select_best_n=
     for k in best:
         trace = []
         try:
-            nn, th, obj = _adam_then_lbfgs(eng, p_init[k].neural, p_init[k].theta, adam_iters, lbfgs_iters, 1e-3,
-                                           callback=lambda _x, l: trace.append(l) and False)
+            if lm:
+                nn, th, obj = _adam_then_lm(eng, p_init[k].neural, p_init[k].theta, adam_iters, lbfgs_iters, 1e-3, trace)
+            else:
+                nn, th, obj = _adam_then_lbfgs(eng, p_init[k].neural, p_init[k].theta, adam_iters, lbfgs_iters, 1e-3,
+                                               callback=lambda _x, l: trace.append(l) and False)
             sols.append(OptimizationSolution(u=ComponentArray(theta=th, neural=nn), objective=obj))
         except FloatingPointError:
             print("Optimization failed")
@@ -1673,6 +1712,19 @@ def network_information(betas, nn, models, timepoints, cpeptide_data, *, sigma, 
     theta = ComponentArray(neural=nn, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
     pop = _params_set(theta, (models, timepoints, cpeptide_data), n_steps)
     return _information(pop.engine, _penalty_weight(sigma, prior_omega))
+
+
+def train_lm(models, timepoints, cpeptide_data, nn, betas, *, max_iters=50, n_trials=4, mu0=1e-2, gtol=0.0, ftol=0.0,
+             n_steps=None):
+    """Levenberg-Marquardt fit of the network parameters and every subject's conditional parameter from (nn, betas) on the
+    device (cude_train_lm: Gauss-Newton steps on network_information's matrices, n_trials dampings tried side by side per
+    iteration).  Returns dict(nn, betas, objective, trace (n_iters + 1,), mu, n_iters, status = one of LM_STATUS)."""
+    theta = ComponentArray(neural=nn, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
+    eng = _params_set(theta, (models, timepoints, cpeptide_data), n_steps).engine
+    res = eng.train_lm(max_iters=max_iters, n_trials=n_trials, mu0=mu0, gtol=gtol, ftol=ftol)
+    nn_out, cond_out = eng.get_params()
+    return {"nn": nn_out, "betas": cond_out, "objective": float(res["trace"][-1]), "trace": res["trace"], "mu": res["mu"],
+            "n_iters": res["n_iters"], "status": LM_STATUS[res["status"]]}
 
 
 def _pinv_sym(m, rcond=1e-12):

@@ -529,6 +529,31 @@ class Engine:
                                                  _ptr(out["qform"]), _ptr(out["status"])))
         return out
 
+    def lm_candidates(self, mu):
+        """Levenberg-Marquardt steps at the context's parameters for the dampings mu (1 ... 8 of them) and their trial
+        losses in one multi-set forward launch (cude_lm_candidates): dict(nn (K, P) = theta + dtheta_k, cond (K, N) = c +
+        dc^k, pred (K,) the predicted reduction of N loss, loss (K,) = multistart_forward at those sets, dnn (K, P) and dcond
+        (K, N) the steps themselves).  An invalid
+        candidate (a pivot of the damped Schur complement not > 0, a failed subject) is NaN throughout.  The context's
+        parameters are untouched."""
+        m = _f64(mu).reshape(-1)
+        K = m.size
+        nn, cond, pred, loss = np.empty((K, self.P)), np.empty((K, self.N)), np.empty(K), np.empty(K)
+        dnn, dcond = np.empty((K, self.P)), np.empty((K, self.N))
+        check(self._lib.cude_lm_candidates(self._h, K, _ptr(m), _ptr(nn), _ptr(cond), _ptr(pred), _ptr(loss), _ptr(dnn),
+                                           _ptr(dcond)))
+        return {"nn": nn, "cond": cond, "pred": pred, "loss": loss, "dnn": dnn, "dcond": dcond}
+
+    def train_lm(self, max_iters=50, n_trials=4, mu0=1e-2, gtol=0.0, ftol=0.0):
+        """Levenberg-Marquardt on the context's parameters (cude_train_lm), which hold the result afterwards: dict(trace
+        (n_iters + 1,) = forward()'s loss at the start and after every iteration, mu (n_iters + 1,), n_iters, status =
+        LM_GRAD | LM_DECREASE | LM_STALLED | LM_MAX_ITERS | LM_FAILED)."""
+        trace, mus = np.full(int(max_iters) + 1, np.nan), np.full(int(max_iters) + 1, np.nan)
+        n, st = C.c_int32(), C.c_int32()
+        check(self._lib.cude_train_lm(self._h, int(max_iters), int(n_trials), float(mu0), float(gtol), float(ftol),
+                                      _ptr(trace), _ptr(mus), C.byref(n), C.byref(st)))
+        return {"trace": trace[:n.value + 1], "mu": mus[:n.value + 1], "n_iters": n.value, "status": st.value}
+
     def fit_conditional(self, lower, upper, n_grid=41, n_iters=48, penalty_weight=0.0, penalty_center=0.0):
         """All subjects' 1-D fits of the conditional parameter with the shared parameters frozen, on the device:
         argmin_x SSE_i(x) + penalty_weight (x - penalty_center)^2 over [lower, upper] -> (x[N], objective[N], sse[N])."""

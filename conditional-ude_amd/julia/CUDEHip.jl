@@ -31,7 +31,7 @@ export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEMod
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
        marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores,
-       network_information, n_outputs
+       network_information, n_outputs, lm_candidates, train_lm!
 
 const LIB = get(ENV, "CUDE_HIP_LIB", "libcude_hip.so")
 const MODEL_CPEP, MODEL_SUPP, MODEL_CPEP_SYM = Int32(0), Int32(1), Int32(2)
@@ -375,6 +375,31 @@ function network_information(c::Ctx; cond = nothing, penalty_weight = 0.0, cov =
         Int32(profiled ? 1 : 0), jac === nothing ? C_NULL : pointer(jac), jcond, gn, coupling, dcond, schur,
         qform === nothing ? C_NULL : pointer(qform), status))
     (; jac, jcond, gn, coupling, dcond, schur, qform, status)
+end
+
+# Levenberg–Marquardt steps at the context's parameters for the dampings μ (1…8) and their trial losses in one multi-set
+# forward launch (cude_lm_candidates): nn P×K = θ + δθₖ, cond N×K = c + δcᵏ, pred = predicted reduction of N·loss, loss =
+# multistart_forward at those sets, dnn / dcond = the steps themselves; an invalid candidate is NaN.  The context's parameters are untouched
+function lm_candidates(c::Ctx, μ::AbstractVector)
+    m = Vector{Float64}(μ); K = length(m)
+    nn = Matrix{Float64}(undef, c.P, K); cond = Matrix{Float64}(undef, c.N, K)
+    pred = Vector{Float64}(undef, K); loss = Vector{Float64}(undef, K)
+    dnn = Matrix{Float64}(undef, c.P, K); dcond = Matrix{Float64}(undef, c.N, K)
+    GC.@preserve m nn cond pred loss dnn dcond check(ccall((:cude_lm_candidates, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, K, m, nn, cond, pred, loss, dnn, dcond))
+    (; nn, cond, pred, loss, dnn, dcond)
+end
+
+# Levenberg–Marquardt on the context's parameters (cude_train_lm): trace = the loss at the start and after every iteration,
+# μ likewise, status 0 gradient ≤ gtol, 1 decrease ≤ ftol·loss, 2 damping left its clamp, 3 iteration budget, 4 failed
+function train_lm!(c::Ctx; max_iters = 50, n_trials = 4, μ0 = 1e-2, gtol = 0.0, ftol = 0.0)
+    trace = fill(NaN, max_iters + 1); μ = fill(NaN, max_iters + 1)
+    n = Ref{Int32}(0); status = Ref{Int32}(0)
+    GC.@preserve trace μ check(ccall((:cude_train_lm, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ref{Int32}, Ref{Int32}),
+        c.h, max_iters, n_trials, Float64(μ0), Float64(gtol), Float64(ftol), trace, μ, n, status))
+    (; trace = trace[1:n[] + 1], μ = μ[1:n[] + 1], n_iters = Int(n[]), status = Int(status[]))
 end
 
 adam_init!(c::Ctx, η; β1 = 0.9, β2 = 0.999, ϵ = 1e-8) =

@@ -569,7 +569,7 @@ int32_t cude_subject_scores(cude_ctx* ctx, int32_t n_sets, const double* cond_se
  *      end (and the one of rule 3).  jac_out is written chunk by chunk.
  * Outputs (all optional, at least one): jac_out [N][n_out][P], jcond_out [N][n_out], gn_out [P][P], coupling_out [N][P],
  * dcond_out [N], schur_out [P][P], qform_out [N][n_out] (needs cov [P][P], finite), status_out [N].
- * Not built: a trainer on these matrices; sharing one forward solve among the outputs of a subject (every output's launch
+ * A trainer on these matrices: cude_train_lm below.  Not built: sharing one forward solve among the outputs of a subject (every output's launch
  * row repeats it); an MFMA cross product; rows from the time-split and five-wave kernels; output times other than the
  * data's. */
 #define CUDE_INFO_FAILED 1
@@ -579,6 +579,71 @@ int32_t cude_network_information(cude_ctx* ctx, const double* cond, double penal
                                  double* schur_out, double* qform_out, int32_t* status_out);
 /* Outputs per subject of cude_network_information (rule 1).  CUDE_ERR_STATE: no population. */
 int32_t cude_n_outputs(cude_ctx* ctx, int32_t* n_out);
+
+/* Levenberg-Marquardt on the matrices of cude_network_information, for the joint fit of the shared parameters theta [P]
+ * and every subject's conditional parameter c_i.  With F = N loss = sum_i sum_o w_o r_io^2 + N lambda |theta|^2, the
+ * half-gradients ghat_theta = sum w_o r_io J_io + N lambda theta and ghat_c,i = sum_o w_o r_io jc_io (N / 2 times what
+ * cude_loss_grad returns) and the Gauss-Newton matrix H = [[A + N lambda I, B], [B^T, D]] (B's column i = b_i, D = diag d_i;
+ * penalty weight 0), a step for the damping mu solves (H + mu M) [dtheta; dc] = -[ghat_theta; ghat_c].
+ *   1. Scaling: M is diagonal, M_theta,q = max(A_qq + N lambda, 1e-8 max_r (A_rr + N lambda)), M_c,i = max(d_i, 1e-8 max_j
+ *      d_j), and 1 wherever that maximum is not > 0.  A FLAT subject (d_i = 0) so gets a damped gradient step.
+ *   2. The solve is by elimination, never as a dense (P + N) system: e_i = d_i + mu M_c,i; S_mu = A + N lambda I + mu
+ *      diag(M_theta) - sum_i b_i b_i^T / e_i; rhs = -(ghat_theta - sum_i b_i ghat_c,i / e_i); S_mu dtheta = rhs by Cholesky;
+ *      dc_i = -(ghat_c,i + b_i . dtheta) / e_i.  Predicted reduction pred = -ghat^T delta + mu delta^T M delta (in units of F;
+ *      > 0 for a valid step).
+ *   3. Order of the sums: sum_i b_i b_i^T / e_i is cude_network_information's cross product (rule 4 there: blocks of 1024
+ *      subjects in index order) over t_i = b_i / sqrt(e_i); the right-hand sides and pred add 256 strided partial sums by a
+ *      halving tree.  Everything is fixed by (N, P) alone: results are bit-identical from run to run.
+ *   4. Cholesky: one workgroup per damping, S_mu in LDS for P <= 86 and in device memory above, up to P = 193 (the largest
+ *      tuned shape; more: CUDE_ERR_UNSUPPORTED).  A pivot that is not > 0 or not finite, a non-finite step, or a FAILED
+ *      subject of the information pass makes that candidate invalid: pred = loss = NaN (and NaN sets from
+ *      cude_lm_candidates); other candidates are not touched.
+ *   5. Parameter mask (cude_set_param_mask): the row and column of a masked entry of S_mu are the unit diagonal, its
+ *      dtheta_q is exactly 0.0 and its value is copied, so that it keeps its bits.
+ *   6. Trial losses: the candidates theta + dtheta_k, c + dc^k are written on the device as the sets of ONE multi-set forward
+ *      launch; a loss is cude_multistart_forward's at that set, bit for bit (+Inf for a failed solve).
+ *   7. Both network models, the symbolic model (P = 1), fixed-step and adaptive mode, every tuned shape and the fallback
+ *      kernel, as cude_network_information (rule 8 there).
+ *   8. CUDE_ERR_STATE: no population or parameters, stream capture.  CUDE_ERR_UNSUPPORTED: a sharded population (a
+ *      communicator or the exchange), P > 193.  CUDE_ERR_ARG: a damping that is not finite and > 0, n_mu / n_trials outside
+ *      1 ... 8, a negative tolerance, max_iters < 0, no output requested.
+ *
+ * cude_lm_candidates: the steps for the caller's dampings mu[n_mu] at the context's current parameters and their trial
+ * losses; changes nothing in the context's parameters.  Outputs (all optional, at least one): nn_out [n_mu][P], cond_out
+ * [n_mu][N], pred_out [n_mu], loss_out [n_mu], and the steps themselves dnn_out [n_mu][P], dcond_out [n_mu][N] (theta + dtheta
+ * rounds, so a small step cannot be recovered from nn_out).
+ *
+ * cude_train_lm: the loop, on the context's parameters (as cude_adam_run leaves its result there).
+ *   9. An iteration is one gradient launch, one information pass, and the K = n_trials dampings mu_k = mu 5^(k - 1),
+ *      k = 0 ... K - 1 (clamped to [1e-15, 1e15]), solved and evaluated side by side.
+ *  10. Selection, on the device by one lane: the candidate with the lowest finite trial loss below the current loss, ties to
+ *      the lower index.  It is copied into the context's parameters and confirmed by the evaluation cude_forward makes there:
+ *      accepted if that loss is finite and below the current one; then it is the current loss, and mu <- mu_k / 5, clamped
+ *      to [1e-15, 1e15].  (The trial launch and cude_forward may take different kernels, whose sums differ in the last
+ *      bits: the trace is cude_forward's value throughout, so that it strictly decreases over accepted iterations and
+ *      cude_forward afterwards returns its last entry bit for bit.)  Otherwise the parameters are restored bit for bit and
+ *      mu <- 25 mu_{K-1}: the next ladder continues this one upwards without a gap.  (The ratio was 3 at first: with
+ *      four rungs a quarter of the iterations of a 12-subject fit were then rejected outright, because the damping that
+ *      works moves by more than 3 between iterations; 5 lost fewer and ended lower from every start tried, 10 did not.)
+ *  11. status: CUDE_LM_GRAD the max-norm of the loss gradient (cude_loss_grad's g_nn and g_cond) at the current point is
+ *      <= gtol (checked before an iteration counts; the parameters are that point); CUDE_LM_DECREASE an accepted
+ *      iteration with old - new <= ftol old; CUDE_LM_STALLED 25 mu_{K-1} left the clamp; CUDE_LM_MAX_ITERS; CUDE_LM_FAILED a
+ *      non-finite loss, a failed subject of the gradient launch or a FAILED subject of the information pass at the current
+ *      point (cude_n_failed counts them): the parameters stay as at the last accepted point.
+ *  12. loss_trace [max_iters + 1] and mu_trace [max_iters + 1] (optional): entry 0 the start, entry t the loss and the
+ *      damping after iteration t, for t <= *n_iters_out; later entries are not written.
+ *  13. Per iteration the host reads five doubles of the device's record, the confirming loss pair and the information
+ *      pass's failure count; never a vector of N entries or a P x P matrix.
+ * Not built: a sharded population; several restarts in one call; box bounds on the conditionals. */
+#define CUDE_LM_GRAD 0
+#define CUDE_LM_DECREASE 1
+#define CUDE_LM_STALLED 2
+#define CUDE_LM_MAX_ITERS 3
+#define CUDE_LM_FAILED 4
+int32_t cude_lm_candidates(cude_ctx* ctx, int32_t n_mu, const double* mu, double* nn_out, double* cond_out, double* pred_out,
+                           double* loss_out, double* dnn_out, double* dcond_out);
+int32_t cude_train_lm(cude_ctx* ctx, int32_t max_iters, int32_t n_trials, double mu0, double gtol, double ftol,
+                      double* loss_trace, double* mu_trace, int32_t* n_iters_out, int32_t* status_out);
 
 /* SAEM E-step on the device: n_mc Metropolis-Hastings steps of every subject's conditional parameter
  * (`mcmc_step` src/saem.jl:86-108, applied n_mcmc_steps times with the stochastic-approximation update of the
