@@ -387,6 +387,149 @@ struct SuppAdTan : SuppAd<W, D, HA, OA> {
     }
 };
 
+// ---------------------------------------------------------------------------------- order-2 policies (cude_curvature)
+// The tangent policies carried one Taylor coefficient further: the state vector is [u; du; d2u], the right-hand side of
+// the third part is the second-order tangent one (Net::eval_jet2), NERR is unchanged -- the accepted steps stay
+// cude_forward's and the result is the second derivative of the accepted-step map.  The primal and first-order operations
+// are those of CpepAdTan / SuppAdTan in the same order.
+template <class Net>
+struct CpepAdCurv : CpepAd<Net> {
+    using Base = CpepAd<Net>;
+    static constexpr int NS = 6, NERR = 2;          // [u1, u2, du1, du2, d2u1, d2u2]
+    static constexpr int WAVES = 1;                 // (2-8-3: 220 bytes of scratch in a 256-register budget)
+    using Args = CpepCurvArgs;
+    double dc[Net::NCST], d2c[Net::NCST];
+    double dbase, d2base, prod_last, dprod_last, d2prod_last, info, score, curv2;
+    __device__ __forceinline__ double init(const Args& a, double* s_extra, int lane_, int64_t i, int64_t set, double (&y)[NS]) {
+        double y2[2];
+        const double chk = Base::init(a, s_extra, lane_, i, set, y2);
+        y[0] = y2[0]; y[1] = y2[1];
+#pragma unroll
+        for (int s = 2; s < NS; s++) y[s] = 0.0;
+        Net::cond_tangent(this->p, this->cst0, dc);
+        Net::cond_tangent2(this->p, this->cst0, d2c);
+        dbase = d2base = prod_last = dprod_last = d2prod_last = info = score = curv2 = 0.0;
+        return chk;
+    }
+    __device__ __forceinline__ void rhs(int st, double te, const double (&Y)[NS], double (&du)[NS]) {
+        // (stage 7 reuses stage 6's value, and the baseline comes first at st == -2: CpepAdTan::rhs)
+        if (st != 6) {
+            const int nr = st == -2 ? 2 : 1;
+#pragma unroll 1
+            for (int r = 0; r < nr; r++) {
+                const bool is_base = st == -2 && r == 0;
+                const double xx[1] = {is_base ? 0.0 : this->forcing_input(te)}, dx[1] = {0.0};
+                double dv, d2v;
+                const double v = Net::template eval_jet2<false>(this->p, this->c, xx, dc, dx, d2c, dx, &dv, &d2v);
+                if (is_base) { this->base = v; dbase = dv; d2base = d2v; }
+                else { prod_last = v; dprod_last = dv; d2prod_last = d2v; }
+            }
+        }
+        du[0] = fma(this->a11, Y[0], fma(this->a12, Y[1], this->f0 + (prod_last - this->base)));
+        du[1] = fma(this->a21, Y[0], this->a22 * Y[1]);
+        du[2] = fma(this->a11, Y[2], fma(this->a12, Y[3], dprod_last - dbase));
+        du[3] = fma(this->a21, Y[2], this->a22 * Y[3]);
+        du[4] = fma(this->a11, Y[4], fma(this->a12, Y[5], d2prod_last - d2base));
+        du[5] = fma(this->a21, Y[4], this->a22 * Y[5]);
+    }
+    __device__ __forceinline__ double residual2(const Args& a, int oi, int64_t i, const double (&o)[NS], bool active) {
+        if (a.out2.sens2 != nullptr && active) {
+            double* tr = a.out2.sens2 + (int64_t)2 * (oi + (int64_t)a.T * i);
+            tr[0] = o[4];
+            tr[1] = o[5];
+        }
+        const double r = o[0] - a.obs[(int64_t)oi * a.N + i];
+        info = fma(o[2], o[2], info);
+        score = fma(r, o[2], score);
+        curv2 = fma(r, o[4], curv2);
+        return r * r;
+    }
+    __device__ __forceinline__ void record(const Args& a, int64_t slot, int n, double, double dt, const double (&)[NS]) const {
+        if (a.tape != nullptr && n < a.tape_cap) a.tape[(int64_t)n * a.N + slot] = dt;
+    }
+    __device__ __forceinline__ void finish(const Args& a, int64_t i, bool active, bool bad) const {
+        if (!active) return;
+        const double nan = __builtin_nan("");
+        if (a.out.info != nullptr) a.out.info[i] = bad ? nan : info;
+        if (a.out.score != nullptr) a.out.score[i] = bad ? nan : score;
+        if (a.out2.curv != nullptr) a.out2.curv[i] = bad ? nan : info + curv2;
+        if (bad && a.out2.sens2 != nullptr)
+            for (int q = 0; q < 2 * a.T; q++) a.out2.sens2[(int64_t)2 * a.T * i + q] = nan;
+    }
+};
+
+template <int W, int D, int HA = kActHiddenTanh, int OA = kActOutSoftplus>
+struct SuppAdCurv : SuppAd<W, D, HA, OA> {
+    using Base = SuppAd<W, D, HA, OA>;
+    using typename Base::Net;
+    static constexpr int NS = 7, NERR = 3;          // [u1, u2, u3, du2, du3, d2u2, d2u3]: state 1 depends on no parameter
+    static constexpr int WAVES = 1;                 // (8-2: 188 bytes of scratch in a 256-register budget)
+    using Args = SuppCurvArgs;
+    double dc[W], d2c[W];
+    double info, score, curv2;
+    __device__ __forceinline__ double init(const Args& a, double*, int, int64_t i, int64_t set, double (&y)[NS]) {
+        double y3[3];
+        const double chk = Base::init(a, nullptr, 0, i, set, y3);
+        y[0] = y3[0]; y[1] = y3[1]; y[2] = y3[2];
+#pragma unroll
+        for (int s = 3; s < NS; s++) y[s] = 0.0;
+        const double cst0 = exp(a.cond[set * a.set_stride_cond + i]);
+        Net::cond_tangent(this->p, cst0, dc);
+        Net::cond_tangent2(this->p, cst0, d2c);
+        info = score = curv2 = 0.0;
+        return chk;
+    }
+    __device__ __forceinline__ void rhs(int, double, const double (&Y)[NS], double (&du)[NS]) const {
+        const double x[3] = {Y[0], Y[1], Y[2]}, dx[3] = {0.0, Y[3], Y[4]}, d2x[3] = {0.0, Y[5], Y[6]};
+        double duh, d2uh;
+        const double uh = Net::template eval_jet2<true>(this->p, this->c, x, dc, dx, d2c, d2x, &duh, &d2uh);
+        du[0] = -0.4 * Y[0];
+        du[1] = fma(0.4, Y[0], -uh);
+        du[2] = fma(-0.3, Y[2], uh);
+        du[3] = -duh;
+        du[4] = fma(-0.3, Y[4], duh);
+        du[5] = -d2uh;
+        du[6] = fma(-0.3, Y[6], d2uh);
+    }
+    __device__ __forceinline__ double residual2(const Args& a, int oi, int64_t i, const double (&o)[NS], bool active) {
+        if (a.out2.sens2 != nullptr && active) {
+            double* tr = a.out2.sens2 + (int64_t)3 * (oi + (int64_t)a.T * i);
+            tr[0] = 0.0;
+            tr[1] = o[5];
+            tr[2] = o[6];
+        }
+        double s2 = 0.0;
+#pragma unroll
+        for (int s = 0; s < 3; s++) {
+            const double r = o[s] - a.data[((int64_t)s * a.T + oi) * a.N + i];
+            s2 = fma(r * a.iscale2[s], r, s2);
+            if (s > 0) {
+                info = fma(o[2 + s] * a.iscale2[s], o[2 + s], info);
+                score = fma(r * a.iscale2[s], o[2 + s], score);
+                curv2 = fma(r * a.iscale2[s], o[4 + s], curv2);
+            }
+        }
+        return s2;
+    }
+    __device__ __forceinline__ void record(const Args& a, int64_t slot, int n, double t, double dt, const double (&y)[NS]) const {
+        if (a.tape == nullptr || n >= a.tape_cap) return;
+        double* e = a.tape + (int64_t)n * kSuppTapeRows * a.N + slot;
+        e[0] = t;
+        e[a.N] = dt;
+#pragma unroll
+        for (int s = 0; s < 3; s++) e[(2 + s) * a.N] = y[s];
+    }
+    __device__ __forceinline__ void finish(const Args& a, int64_t i, bool active, bool bad) const {
+        if (!active) return;
+        const double nan = __builtin_nan("");
+        if (a.out.info != nullptr) a.out.info[i] = bad ? nan : info;
+        if (a.out.score != nullptr) a.out.score[i] = bad ? nan : score;
+        if (a.out2.curv != nullptr) a.out2.curv[i] = bad ? nan : info + curv2;
+        if (bad && a.out2.sens2 != nullptr)
+            for (int q = 0; q < 3 * a.T; q++) a.out2.sens2[(int64_t)3 * a.T * i + q] = nan;
+    }
+};
+
 __device__ __forceinline__ double rms(const double* v, int n) {
     double s = 0.0;
     for (int k = 0; k < n; k++) s = fma(v[k], v[k], s);
@@ -395,8 +538,18 @@ __device__ __forceinline__ double rms(const double* v, int n) {
 
 // waves per SIMD the register allocation aims at: the solve is a latency chain, so a second resident wave is worth more
 // than unrolling room, as long as the gradient accumulators (2 VGPRs each) leave space for it
+// (a policy with a member WAVES names its own: the order-2 policies, whose widest shapes spill at two)
+template <class M, class = void>
+struct AdWaves {
+    static constexpr int value = 0;
+};
+template <class M>
+struct AdWaves<M, decltype((void)M::WAVES)> {
+    static constexpr int value = M::WAVES;
+};
 template <class M, bool GRAD>
 constexpr int adaptive_waves() {
+    if (AdWaves<M>::value > 0) return AdWaves<M>::value;
     return !GRAD ? 2 : (M::NetT::NACC <= (M::NEED_Y ? 24 : CUDE_ADAPT_2W_NACC) ? 2 : 1);
 }
 

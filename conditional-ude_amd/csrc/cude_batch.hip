@@ -613,6 +613,50 @@ int32_t cude_sensitivity(cude_ctx* c, double* sens, double* info, double* score,
     return finish_loss(c, nullptr, nullptr);
 }
 
+int32_t cude_curvature(cude_ctx* c, double* sens2, double* curv, double* info, double* score, double* sse) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn || !c->have_cond) return fail(CUDE_ERR_STATE, "parameters not set");
+    if (c->net.generic())
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_curvature: the network of this context runs on the fallback kernel "
+                                          "(cude_set_network), which has no forward-mode solve");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_curvature under stream capture");
+    if (!sens2 && !curv && !info && !score && !sse) return fail(CUDE_ERR_ARG, "cude_curvature: no output requested");
+    const bool cpep = is_cpep(c);
+    const int NS = cpep ? c->cfg.n_state : 3;
+    const int64_t N = c->N;
+    if (sens2) HIP_TRY(c->sens2.reserve((size_t)NS * c->T * N));
+    HIP_TRY(c->sens_curv.reserve((size_t)N));
+    HIP_TRY(c->sens_info.reserve((size_t)N));
+    HIP_TRY(c->sens_score.reserve((size_t)N));
+    // adaptive mode: the accepted steps go to the gradient's tape, so that cude_adaptive_steps reports them
+    if (adaptive(c) && (rc = ensure_tape(c))) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->timing && (c->timing_count++ % c->timing_period) == 0 && (rc = timed_pair(c, &e0, &e1))) return rc;
+    cude::SensOut out;
+    out.info = c->sens_info.p;
+    out.score = c->sens_score.p;
+    cude::CurvOut out2;
+    out2.sens2 = sens2 ? c->sens2.p : nullptr;
+    out2.curv = c->sens_curv.p;
+    const hipError_t le = launch_tangent2(c, c->cond.p, c->sse.p, out, out2, true);
+    if (le == hipErrorInvalidValue) return fail(CUDE_ERR_UNSUPPORTED, "cude_curvature: no order-2 kernel compiled for this network shape / model");
+    HIP_TRY(le);
+    if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
+    note_adaptive_launch(c, true);
+    // [sum SSE, n_failed] behind the launch, as cude_sensitivity
+    c->loss_in_pinned = false;
+    c->tail_in_pinned = false;
+    HIP_TRY(cude::launch_reduce_cols(c->partials.p, c->nblocks, c->P + 2, c->P, 2, c->g_nn.p, c->stream));
+    HIP_TRY(fetch(c, sens2, c->sens2.p, (size_t)NS * c->T * N));
+    HIP_TRY(fetch(c, curv, c->sens_curv.p, N));
+    HIP_TRY(fetch(c, info, c->sens_info.p, N));
+    HIP_TRY(fetch(c, score, c->sens_score.p, N));
+    HIP_TRY(fetch(c, sse, c->sse.p, N));
+    return finish_loss(c, nullptr, nullptr);
+}
+
 int32_t cude_multistart_forward(cude_ctx* c, int32_t n_sets, const double* nn_sets, const double* cond_sets,
                                 double* losses) {
     int32_t rc = bind(c);

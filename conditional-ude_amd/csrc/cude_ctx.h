@@ -168,6 +168,7 @@ struct cude_ctx {
     // parameters / gradients / optimiser
     cude::api::DevBuf<double> nn, cond, g_nn, g_cond, sse, auc, partials, traj;
     cude::api::DevBuf<double> sens, sens_info, sens_score;     // cude_sensitivity: [n_state x T x N], [N], [N] (first call)
+    cude::api::DevBuf<double> sens2, sens_curv;                // cude_curvature: [n_state x T x N], [N] (first call)
     cude::api::DevBuf<double> refine_buf;                      // cude_refine_conditional: 13 rows of N (first call; kept, so that
     cude::api::DevBuf<int32_t> refine_ibuf;                    // ... repeated fits -- SAEM's MAP step -- do not allocate): 2 rows
     // chunked gradient path (cude_cpep2.hip)
@@ -370,6 +371,9 @@ struct SetsRows {
 int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t stride_nn, const double* cond,
                          int64_t stride_cond, double* g_cond, double* out, const SetsRows* rows = nullptr);
 hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, bool keep_tape);
+// ... one order-2 solve (cude_curv.hip): `out.sens` is not written, `out2` holds the second-order outputs
+hipError_t launch_tangent2(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, const cude::CurvOut& out2,
+                           bool keep_tape);
 // A forward solve of n_sets parameter sets in one launch (set k: nn + k * stride_nn, cond + k * N; the set index is a grid
 // dimension): what the entry points that batch solves differ in.  The rest of the launch is forward_sets's.
 struct SetsForward {

@@ -168,6 +168,19 @@ __device__ __forceinline__ double act_hidden_deriv(double h) {
     else if constexpr (HA == kActHiddenSigmoid) return h * (1.0 - h);
     else return 1.0;
 }
+// second derivative, again from the output h (order-2 forward mode, eval_jet2)
+template <int HA>
+__device__ __forceinline__ double act_hidden_deriv2(double h) {
+    if constexpr (HA == kActHiddenTanh) return -2.0 * h * fma(-h, h, 1.0);
+    else if constexpr (HA == kActHiddenSigmoid) return h * (1.0 - h) * fma(-2.0, h, 1.0);
+    else return 0.0;                                                           // relu (also at the kink), identity
+}
+// ... and of the output unit, from the `sig` that act_out returns: softplus'' = sig (1 - sig)
+template <int OA>
+__device__ __forceinline__ double act_out_deriv2(double sig) {
+    if constexpr (OA == kActOutSoftplus) return sig * (1.0 - sig);
+    else return 0.0;
+}
 // output unit: value and derivative
 template <int OA, bool LONE, bool LEAN = false>
 __device__ __forceinline__ double act_out(double x, double* sig) {
@@ -1175,6 +1188,97 @@ struct Mlp {
         *dy = sig * (d0 + d1);
         return y;
     }
+
+    // ---- order-2 forward mode (cude_curvature): the first three Taylor coefficients of the output along one curve
+    // through the inputs.  d^2 c_j / d(conditional)^2: the conditional enters as exp(value), so both orders carry the same
+    // chain factor
+    __device__ static __forceinline__ void cond_tangent2(cptr_t p, double cst0, double (&d2c)[W]) { cond_tangent(p, cst0, d2c); }
+    // Value, first and second directional derivative in one sweep.  The curve's velocity is (dx, dc) and its acceleration
+    // (d2x, d2c) (HAS_DX; otherwise the variable inputs do not move).  Per layer z, dz, d2z come from one fetch of each
+    // weight column feeding three multiply-adds; then h = a(z), dh = a' dz, d2h = a' d2z + a'' dz^2.  The primal
+    // operations are those of `eval`, in the same order, and the first-order ones those of eval_jvp.
+    template <bool HAS_DX>
+    __device__ static __forceinline__ double eval_jet2(cptr_t p, const double (&c)[W], const double (&x)[NV],
+                                                       const double (&dc)[W], const double (&dx)[NV], const double (&d2c)[W],
+                                                       const double (&d2x)[NV], double* dy, double* d2y) {
+        p = launder(p);
+        double z[W], dz[W], d2z[W], h[W], dh[W], d2h[W];
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            const SCol<W> col = ld_col<W>(p, W * i);
+#pragma unroll
+            for (int j = 0; j < W; j++) {
+                z[j] = fma(col.v[j], x[i], i == 0 ? c[j] : z[j]);
+                if (HAS_DX) {
+                    dz[j] = fma(col.v[j], dx[i], i == 0 ? dc[j] : dz[j]);
+                    d2z[j] = fma(col.v[j], d2x[i], i == 0 ? d2c[j] : d2z[j]);
+                }
+            }
+        }
+        if (!HAS_DX) {
+#pragma unroll
+            for (int j = 0; j < W; j++) { dz[j] = dc[j]; d2z[j] = d2c[j]; }
+        }
+        act_hidden_vec<W, HA, TT>(z, h);
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            const double a1 = act_hidden_deriv<HA>(h[j]);
+            dh[j] = a1 * dz[j];
+            d2h[j] = fma(act_hidden_deriv2<HA>(h[j]) * dz[j], dz[j], a1 * d2z[j]);
+        }
+#pragma unroll
+        for (int l = 1; l < D; l++) {
+            const int o = L1 + (l - 1) * LH;
+            CUDE_FENCE();
+            if constexpr (LDS_BIAS) {
+#pragma unroll
+                for (int j = 0; j < W; j++) z[j] = s_bias[(l - 1) * W + j];
+            } else {
+                const SCol<W> b = ld_col<W>(p, o + W * W);
+#pragma unroll
+                for (int j = 0; j < W; j++) z[j] = seed_from_sgpr(b.v[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < W; j++) { dz[j] = 0.0; d2z[j] = 0.0; }
+#pragma unroll
+            for (int i0 = 0; i0 < W; i0 += CG) {
+                CUDE_FENCE();
+                constexpr int kG = CG;
+                const SCol<W * kG> col = ld_col<W * kG>(p, o + W * i0);
+#pragma unroll
+                for (int g = 0; g < kG; g++)
+#pragma unroll
+                    for (int j = 0; j < W; j++)
+                        if (i0 + g < W) {
+                            z[j] = fma(col.v[g * W + j], h[i0 + g], z[j]);
+                            dz[j] = fma(col.v[g * W + j], dh[i0 + g], dz[j]);
+                            d2z[j] = fma(col.v[g * W + j], d2h[i0 + g], d2z[j]);
+                        }
+            }
+            CUDE_FENCE();
+            act_hidden_vec<W, HA, TT>(z, h);
+#pragma unroll
+            for (int j = 0; j < W; j++) {
+                const double a1 = act_hidden_deriv<HA>(h[j]);
+                dh[j] = a1 * dz[j];
+                d2h[j] = fma(act_hidden_deriv2<HA>(h[j]) * dz[j], dz[j], a1 * d2z[j]);
+            }
+        }
+        CUDE_FENCE();
+        const SCol<W> wo = ld_col<W>(p, OUT);
+        double z0 = seed_from_sgpr(p[OUT + W]), z1 = 0.0, d0 = 0.0, d1 = 0.0, e0 = 0.0, e1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            if (i & 1) { z1 = fma(wo.v[i], h[i], z1); d1 = fma(wo.v[i], dh[i], d1); e1 = fma(wo.v[i], d2h[i], e1); }
+            else { z0 = fma(wo.v[i], h[i], z0); d0 = fma(wo.v[i], dh[i], d0); e0 = fma(wo.v[i], d2h[i], e0); }
+        }
+        double sig;
+        const double y = act_out<OA, TT>(z0 + z1, &sig);
+        const double dzo = d0 + d1;
+        *dy = sig * dzo;
+        *d2y = fma(act_out_deriv2<OA>(sig) * dzo, dzo, sig * (e0 + e1));
+        return y;
+    }
 };
 
 // the networks of the fixed-step kernel families with their tanh form (see act_tanh_vec)
@@ -1283,6 +1387,32 @@ struct MmProd {
         if (HAS_DX) d = fma(p0 * c[0] * r * r, dx[0], d);    // d/dx
         const bool pos = x[0] >= 0.0;
         *dy = pos ? d : 0.0;
+        return pos ? v : 0.0;
+    }
+    // ---- order-2 forward mode, as Mlp, in closed form: with r = 1 / (x + k)
+    //   v_k = -p0 x r^2, v_kk = 2 p0 x r^3, v_x = p0 k r^2, v_xx = -2 p0 k r^3, v_xk = p0 (x - k) r^3
+    // and k = exp(cond) unless RAW: d^2 v / d cond^2 = v_kk k^2 + v_k k.  All derivatives are 0 for x < 0.
+    __device__ static __forceinline__ void cond_tangent2(cptr_t, double cst0, double (&d2c)[1]) { d2c[0] = RAW ? 0.0 : cst0; }
+    template <bool HAS_DX>
+    __device__ static __forceinline__ double eval_jet2(cptr_t p, const double (&c)[1], const double (&x)[1],
+                                                       const double (&dc)[1], const double (&dx)[1], const double (&d2c)[1],
+                                                       const double (&d2x)[1], double* dy, double* d2y) {
+        const double p0 = p[0];
+        const double v = (p0 * x[0]) / (x[0] + c[0]);
+        const double r = 1.0 / (x[0] + c[0]);
+        const double vk = -(p0 * x[0]) * r * r;
+        double d = vk * dc[0];
+        double d2 = fma(2.0 * (p0 * x[0]) * r * r * r * dc[0], dc[0], vk * d2c[0]);
+        if (HAS_DX) {
+            const double vx = p0 * c[0] * r * r;
+            d = fma(vx, dx[0], d);
+            d2 = fma(vx, d2x[0], d2);
+            d2 = fma(2.0 * p0 * (x[0] - c[0]) * r * r * r * dc[0], dx[0], d2);
+            d2 = fma(-2.0 * p0 * c[0] * r * r * r * dx[0], dx[0], d2);
+        }
+        const bool pos = x[0] >= 0.0;
+        *dy = pos ? d : 0.0;
+        *d2y = pos ? d2 : 0.0;
         return pos ? v : 0.0;
     }
 };

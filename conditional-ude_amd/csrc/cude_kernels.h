@@ -308,6 +308,22 @@ struct SuppSensArgs : SuppArgs {
 hipError_t launch_cpep_sens(const NetShape& net, int n_state, const CpepSensArgs& a, hipStream_t s);
 hipError_t launch_supp_sens(const NetShape& net, const SuppSensArgs& a, hipStream_t s);
 
+// Order-2 forward-mode solves, cude_curvature (cude_curv.hip): cude_sensitivity's blocks plus the two second-order outputs
+// (`out.sens` is not written by these launches).  One parameter set, one lane per subject.
+struct CurvOut {
+    double* sens2 = nullptr; // [n_state x T x N] column-major: d^2 u_s(t_j) / d cond_i^2
+    double* curv = nullptr;  // [N] info + sum of w^2 (yhat - y) d^2 yhat / d cond^2 = (1/2) d^2 SSE_i / d cond_i^2
+};
+struct CpepCurvArgs : CpepSensArgs {
+    CurvOut out2;
+};
+struct SuppCurvArgs : SuppSensArgs {
+    CurvOut out2;
+};
+// hipErrorInvalidValue when no tuned kernel is compiled for the shape, as launch_*_sens
+hipError_t launch_cpep_curv(const NetShape& net, int n_state, const CpepCurvArgs& a, hipStream_t s);
+hipError_t launch_supp_curv(const NetShape& net, const SuppCurvArgs& a, hipStream_t s);
+
 // the fallback kernel for networks no tuned kernel is compiled for (net.generic(); cude_generic.hip)
 hipError_t launch_cpep_generic(const NetShape& net, int n_state, bool grad, const CpepArgs& a, hipStream_t s);
 hipError_t launch_supp_generic(const NetShape& net, bool grad, const SuppArgs& a, hipStream_t s);

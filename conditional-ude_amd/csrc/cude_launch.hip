@@ -567,6 +567,27 @@ hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cu
     return cude::launch_supp_sens(c->net, a, c->stream);
 }
 
+hipError_t launch_tangent2(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, const cude::CurvOut& out2,
+                           bool keep_tape) {
+    const auto fill = [&](auto& a) {
+        a.cond = cond; a.nn = c->nn.p; a.sse = sse; a.partials = c->partials.p;
+        if (!keep_tape) a.tape = nullptr;
+        a.out = out;
+        a.out.sens = nullptr;
+        a.out2 = out2;
+    };
+    if (is_cpep(c)) {
+        cude::CpepCurvArgs a{};
+        static_cast<cude::CpepArgs&>(a) = cpep_args(c);
+        fill(a);
+        return cude::launch_cpep_curv(c->net, c->cfg.n_state, a, c->stream);
+    }
+    cude::SuppCurvArgs a{};
+    static_cast<cude::SuppArgs&>(a) = supp_args(c);
+    fill(a);
+    return cude::launch_supp_curv(c->net, a, c->stream);
+}
+
 // (SetsForward: cude_ctx.h)
 // Scratch of forward_sets for up to max_sets sets per launch.  A split launch works in the context's own (ms_fsum: every
 // set's forced chunk responses, ms_part: kept between calls), any other in the caller's `own_part`, which goes into

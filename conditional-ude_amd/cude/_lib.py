@@ -96,6 +96,7 @@ _SIGNATURES = {
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "cude_n_failed": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),
     "cude_sensitivity": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cude_curvature": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cude_adam_init": (C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]),
     "cude_adam_step": (C.c_int32, [C.c_void_p, _dp]),
     "cude_synchronize": (C.c_int32, [C.c_void_p]),

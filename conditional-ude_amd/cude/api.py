@@ -973,13 +973,37 @@ def sensitivities(theta, args, *, n_steps=None):
     return out["sens"], out["info"], out["score"], out["sse"]
 
 
+def curvatures(theta, args, *, n_steps=None):
+    """Exact curvature of every subject's objective in its own conditional parameter, by the library's order-2
+    forward-mode solve (cude_curvature) -- what ForwardDiff.hessian of the per-subject objective gives.  args and theta as
+    `sensitivities`.  Returns (sens2 (n_state, T, N) = d^2 u_s(t_j) / d beta_i^2, curv (N,) = sum_j [(d yhat_j / d beta_i)^2
+    + (yhat_j - y_j) d^2 yhat_j / d beta_i^2] = half the second derivative of SSE_i, info, score, sse (N,) as
+    `sensitivities`).  curv / sigma^2 is the OBSERVED information; unlike info it may be <= 0 (the point is then no minimum
+    of SSE_i).  Failed subjects are NaN."""
+    out = _params_set(theta, args, n_steps).engine.curvature()
+    return out["sens2"], out["curv"], out["info"], out["score"], out["sse"]
+
+
+def _information_kind(information):
+    if information not in ("expected", "observed"):
+        raise ValueError('information must be "expected" or "observed"')
+    return information == "observed"
+
+
 def conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data, *, sigma=None,
-                                n_steps=None, info=None, sse=None):
+                                n_steps=None, info=None, sse=None, information="expected"):
     """Asymptotic standard error of every subject's conditional parameter: sigma / sqrt(info_i), the inverse square root
     of the Fisher information info_i / sigma^2 of a Gaussian error model.  sigma = None: the per-subject maximum-likelihood
     value sigma_i^2 = SSE_i / n_i, the closed form loss_sigma (src/parameter-estimation.jl:70-75) is minimised by.  A
     subject whose data do not identify the parameter (info = 0) gets inf.  info (and sse, unless sigma is given): what a
-    fit with method = "newton" returned at betas (estimate_conditional(..., return_info=True)) -- no second solve."""
+    fit with method = "newton" returned at betas (estimate_conditional(..., return_info=True)) -- no second solve.
+    information = "observed": the observed information curv_i / sigma^2 of `curvatures` takes the place of the expected
+    one (one cude_curvature call; `info` is not used): se = sigma / sqrt(curv_i) where curv_i > 0, inf where curv_i <= 0
+    (betas_i is no minimum of SSE_i), NaN for a failed subject."""
+    if _information_kind(information):
+        theta = ComponentArray(neural=neural_network_parameters, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
+        _, curv, _, _, sse = curvatures(theta, (models, timepoints, cpeptide_data), n_steps=n_steps)
+        return _standard_errors(curv, sse, len(timepoints), sigma)
     if info is not None and (sigma is not None or sse is not None):
         return _standard_errors(info, np.zeros_like(info) if sse is None else sse, len(timepoints), sigma)
     theta = ComponentArray(neural=neural_network_parameters, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
@@ -1003,11 +1027,12 @@ def _wald(betas, se, level):
 
 
 def wald_confidence_intervals(betas, neural_network_parameters, models, timepoints, cpeptide_data, *, sigma=None,
-                              level=0.95, n_steps=None):
+                              level=0.95, n_steps=None, information="expected"):
     """Wald intervals beta_i -/+ z_level * se_i, one (lower, upper) pair per subject as find_confidence_intervals returns
-    for a profile; (-inf, inf) where the data do not identify the parameter."""
+    for a profile; (-inf, inf) where the data do not identify the parameter.  information: as
+    conditional_standard_errors."""
     se = conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data, sigma=sigma,
-                                     n_steps=n_steps)
+                                     n_steps=n_steps, information=information)
     return _wald(betas, se, level)
 
 
@@ -1105,6 +1130,16 @@ def suppression_sensitivities(p, args, *, n_steps=None):
     pop.engine.set_params(p.neural, p.theta)
     out = pop.engine.sensitivity()
     return out["sens"], out["info"], out["score"], out["sse"]
+
+
+def suppression_curvatures(p, args, *, n_steps=None):
+    """curvatures for the suppression model: args as suppression_sensitivities.  Returns (sens2 (3, T, N) = d^2 u / d
+    theta_i^2 (state 1 exactly 0), curv, info, score, sse) with the loss's weights 1 / scale_s."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, p.theta)
+    out = pop.engine.curvature()
+    return out["sens2"], out["curv"], out["info"], out["score"], out["sse"]
 
 
 def suppression_profile_intervals(p, args, lower_bound, upper_bound, sigma, *, steps=1000, target="cantelli95", rounds=0,
@@ -1515,11 +1550,18 @@ def grid_rule(lo, hi, n):
 
 
 def _marginal_solve(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, method, n_nodes,
-                    grid_halfwidth, lower, upper, first_step, seed, n_steps, want=False, center=None, scale=None):
+                    grid_halfwidth, lower, upper, first_step, seed, n_steps, want=False, center=None, scale=None,
+                    curvature="expected", fallback=None):
     """The rule of marginal_likelihood and its device call: (population, the engine's dict, center, scale).  want: the
-    points and terms as well.  center / scale given: the rule is placed there instead of at the MAP (not for "grid")."""
-    if method not in ("quadrature", "grid", "importance"):
-        raise ValueError('method must be "quadrature", "grid" or "importance"')
+    points and terms as well.  center / scale given: the rule is placed there instead of at the MAP (not for "grid").
+    curvature = "observed": the scale comes from one cude_curvature call at the refined centres; the subjects that keep
+    the expected scale (curv + pw <= 0, or no finite curvature) are appended to the list `fallback`."""
+    if method not in ("quadrature", "grid", "importance", "laplace"):
+        raise ValueError('method must be "quadrature", "grid", "importance" or "laplace"')
+    if curvature not in ("expected", "observed"):
+        raise ValueError('curvature must be "expected" or "observed"')
+    if method == "laplace":
+        method, n_nodes = "quadrature", 1
     sym = isinstance(models[0], CPeptideODEModel)
     pop = _population(models, timepoints, cpeptide_data, n_steps, cond_space="raw" if sym else "log")
     eng, N = pop.engine, pop.N
@@ -1537,6 +1579,14 @@ def _marginal_solve(betas, nn, models, timepoints, cpeptide_data, sigma, prior_m
             center, _, _, info = _fit_box(eng, lower, upper, 81 if start is None else 0, 48, "newton", start=start,
                                           penalty_weight=pw, penalty_center=prior_mean)
             scale = sigma / np.sqrt(info + pw)
+            if curvature == "observed":
+                eng.set_params(None, center)                  # (the cached engine's conditionals: every call sets its own)
+                curv = eng.curvature(want_sens2=False)["curv"]
+                with np.errstate(invalid="ignore"):
+                    ok = curv + pw > 0.0                      # (False for NaN as well)
+                    scale = np.where(ok, sigma / np.sqrt(np.where(ok, curv + pw, 1.0)), scale)
+                if fallback is not None:
+                    fallback.extend(int(i) for i in np.flatnonzero(~ok))
         if method == "quadrature":
             z, a = gauss_hermite_rule(n_nodes)
             r = eng.marginal_likelihood(sigma, prior_mean, omega, nodes=z, log_weights=a, center=center, scale=scale,
@@ -1551,24 +1601,34 @@ def _marginal_solve(betas, nn, models, timepoints, cpeptide_data, sigma, prior_m
 
 def marginal_likelihood(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega, *, method="quadrature",
                         n_nodes=33, grid_halfwidth=8.0, lower=-6.0, upper=4.0, first_step=0, seed=None, normalized=False,
-                        n_steps=None):
+                        n_steps=None, curvature="expected"):
     """Every subject's marginal log-likelihood log integral exp(individual_log_likelihood(eta) + logpdf(Normal(prior_mean,
     omega), eta)) d eta (src/saem.jl:55-66) with the network frozen, on the device (cude_marginal_likelihood).
     method = "quadrature": the n_nodes-point Gauss-Hermite rule centred at every subject's MAP -- refine_conditional with
     penalty weight (sigma / omega)^2 from betas (None: an 81-point scan over [lower, upper] first) -- with the Laplace
     scale sigma / sqrt(info + (sigma / omega)^2).  "importance": n_nodes device draws from that normal (steps first_step
     ... of the device stream; seed: set_rng first), self-normalised.  "grid": the trapezoid rule on n_nodes points over
-    prior_mean -/+ grid_halfwidth omega, which needs no centre and misses no mode inside the range.
+    prior_mean -/+ grid_halfwidth omega, which needs no centre and misses no mode inside the range.  "laplace": the
+    one-point rule ("quadrature" with n_nodes = 1), f(MAP) scale sqrt(2 pi).
+    curvature = "observed" ("quadrature", "importance", "laplace"): the scale is sigma / sqrt(curv + (sigma / omega)^2) with
+    the exact curvature of `curvatures` at the refined centres (one cude_curvature call) -- with "laplace" the textbook
+    Laplace approximation.  A subject with curv + (sigma / omega)^2 <= 0, whose centre is no minimum, keeps the expected
+    scale; the result then also has curvature_fallback, the indices of those subjects.
     Returns a namespace: logml, post_mean, post_var, post_sse, ess (N,), n_bad (N,) int32, center, scale (N,), and total =
     the sum of logml in subject order.  The likelihood follows the reference's convention (no 2 pi constant);
     normalized = True adds -(T/2) log(2 pi) per subject."""
+    fallback = []
     pop, r, center, scale = _marginal_solve(betas, nn, models, timepoints, cpeptide_data, sigma, prior_mean, omega,
                                             method=method, n_nodes=n_nodes, grid_halfwidth=grid_halfwidth, lower=lower,
-                                            upper=upper, first_step=first_step, seed=seed, n_steps=n_steps)
+                                            upper=upper, first_step=first_step, seed=seed, n_steps=n_steps,
+                                            curvature=curvature, fallback=fallback)
     logml = r["logml"] - 0.5 * pop.T * math.log(2.0 * math.pi) if normalized else r["logml"]
-    return SimpleNamespace(logml=logml, total=float(np.add.accumulate(logml)[-1]), post_mean=r["post_mean"],
-                           post_var=r["post_var"], post_sse=r["post_sse"], ess=r["ess"], n_bad=r["n_bad"], center=center,
-                           scale=scale)
+    out = SimpleNamespace(logml=logml, total=float(np.add.accumulate(logml)[-1]), post_mean=r["post_mean"],
+                          post_var=r["post_var"], post_sse=r["post_sse"], ess=r["ess"], n_bad=r["n_bad"], center=center,
+                          scale=scale)
+    if curvature == "observed":
+        out.curvature_fallback = np.array(fallback, dtype=np.int64)
+    return out
 
 
 def posterior_weights(terms, logml, scale=None):
@@ -1712,6 +1772,23 @@ def network_information(betas, nn, models, timepoints, cpeptide_data, *, sigma, 
     theta = ComponentArray(neural=nn, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
     pop = _params_set(theta, (models, timepoints, cpeptide_data), n_steps)
     return _information(pop.engine, _penalty_weight(sigma, prior_omega))
+
+
+def map_curvature(betas, nn, models, timepoints, cpeptide_data, *, sigma, prior_omega=None, n_steps=None):
+    """Is every subject's fitted conditional a minimum of its MAP objective SSE_i + pw (beta - prior mean)^2?  One
+    cude_curvature call at betas.  Returns a namespace of (N,) arrays: observed = curv + pw (half the second derivative of
+    the objective; <= 0: no minimum), expected = info + pw (its Gauss-Newton part, what the fits and the Laplace scale
+    use), ratio = observed / expected, and status: "minimum", "not_a_minimum" (observed <= 0) or "failed" (a failed
+    subject).  pw = sigma^2 / prior_omega^2 when the conditionals have a Gaussian prior of standard deviation prior_omega,
+    else 0 (the prior's mean does not enter a second derivative)."""
+    theta = ComponentArray(neural=nn, conditional=np.asarray(betas, dtype=np.float64).reshape(-1))
+    _, curv, info, _, _ = curvatures(theta, (models, timepoints, cpeptide_data), n_steps=n_steps)
+    pw = _penalty_weight(sigma, prior_omega)
+    observed, expected = curv + pw, info + pw
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = observed / expected
+        status = np.where(np.isnan(observed), "failed", np.where(observed > 0.0, "minimum", "not_a_minimum"))
+    return SimpleNamespace(observed=observed, expected=expected, ratio=ratio, status=status)
 
 
 def train_lm(models, timepoints, cpeptide_data, nn, betas, *, max_iters=50, n_trials=4, mu0=1e-2, gtol=0.0, ftol=0.0,

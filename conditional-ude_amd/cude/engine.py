@@ -264,6 +264,16 @@ class Engine:
         check(self._lib.cude_sensitivity(self._h, _ptr(sens), _ptr(info), _ptr(score), _ptr(sse)))
         return {"sens": None if sens is None else sens.transpose(2, 1, 0), "info": info, "score": score, "sse": sse}
 
+    def curvature(self, want_sens2=True):
+        """cude_curvature at the context's parameters: dict(sens2 (n_state, T, N) = d^2 u / d cond_i^2 (None unless
+        want_sens2), curv (N,) = (1/2) d^2 SSE_i / d cond_i^2 (may be <= 0), info (N,), score (N,), sse (N,)); failed
+        subjects are NaN."""
+        sens2 = np.empty((self.N, self.T, self.n_state)) if want_sens2 else None
+        curv, info, score, sse = np.empty(self.N), np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        check(self._lib.cude_curvature(self._h, _ptr(sens2), _ptr(curv), _ptr(info), _ptr(score), _ptr(sse)))
+        return {"sens2": None if sens2 is None else sens2.transpose(2, 1, 0), "curv": curv, "info": info, "score": score,
+                "sse": sse}
+
     def multistart_forward(self, nn_sets, cond_sets):
         """Losses of K candidate (network, conditional) parameter sets in one launch.
         nn_sets: (K, P); cond_sets: (K, N)."""

@@ -30,6 +30,7 @@ export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEMod
        profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
+       curvatures, suppression_curvatures, map_curvature,
        marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores,
        network_information, n_outputs, lm_candidates, train_lm!
 
@@ -145,6 +146,18 @@ function sensitivity(c::Ctx; want_sens = true)
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
         c.h, sens === nothing ? C_NULL : pointer(sens), info, score, sse))
     sens, info, score, sse
+end
+
+# exact curvature in every subject's own conditional parameter (order-2 forward-mode solve): sens2 [n_state × T × N] =
+# ∂²u/∂condᵢ², curv [N] = ½ ∂²SSEᵢ/∂condᵢ² (may be ≤ 0), info, score, sse [N] as sensitivity; failed subjects are NaN
+function curvature(c::Ctx; want_sens2 = true)
+    sens2 = want_sens2 ? Array{Float64,3}(undef, c.n_state, c.T, c.N) : nothing
+    curv = Vector{Float64}(undef, c.N); info = Vector{Float64}(undef, c.N)
+    score = Vector{Float64}(undef, c.N); sse = Vector{Float64}(undef, c.N)
+    GC.@preserve sens2 curv info score sse check(ccall((:cude_curvature, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, sens2 === nothing ? C_NULL : pointer(sens2), curv, info, score, sse))
+    sens2, curv, info, score, sse
 end
 
 # states of every subject at arbitrary times inside the time span: [n_state × n_times × N]
@@ -1020,13 +1033,30 @@ function sensitivities(θ, (models, timepoints, cpeptide_data); n_steps = nothin
     set_params!(c, θ.neural, θ.conditional)
     sensitivity(c)
 end
+# curvatures(θ, args) -> (sens2, curv, info, score, sse): the exact curvature ½ ∂²SSEᵢ/∂βᵢ² next to its Gauss-Newton part
+# info, by cude_curvature; curv / σ² is the observed information and may be ≤ 0
+function curvatures(θ, (models, timepoints, cpeptide_data); n_steps = nothing)
+    c = population(models, timepoints, cpeptide_data; n_steps = n_steps)
+    set_params!(c, θ.neural, θ.conditional)
+    curvature(c)
+end
+information_kind(information) = information in (:expected, :observed) ? information == :observed :
+                                error("information must be :expected or :observed")
 function standard_errors(info, sse, n_obs, sigma)
     [isnan(info[i]) ? NaN : info[i] > 0 ? (sigma === nothing ? sqrt(sse[i] / n_obs) : sigma) / sqrt(info[i]) : Inf
      for i in eachindex(info)]
 end
 # σ / √infoᵢ; sigma = nothing: σᵢ² = SSEᵢ / nᵢ (the closed form loss_sigma is minimised by); info = 0 -> Inf
 function conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data;
-                                     sigma = nothing, n_steps = nothing, info = nothing, sse = nothing)
+                                     sigma = nothing, n_steps = nothing, info = nothing, sse = nothing,
+                                     information = :expected)
+    # information = :observed: σ / √curvᵢ where curvᵢ > 0, Inf where curvᵢ ≤ 0, NaN for a failed subject (one
+    # cude_curvature call; `info` is not used)
+    if information_kind(information)
+        _, curv, _, _, sse2 = curvatures((neural = neural_network_parameters, conditional = betas),
+                                         (models, timepoints, cpeptide_data); n_steps = n_steps)
+        return standard_errors(curv, sse2, length(timepoints), sigma)
+    end
     # info (and sse, unless sigma is given): what a fit with method = newton returned at betas -- no second solve
     if info !== nothing && (sigma !== nothing || sse !== nothing)
         return standard_errors(info, sse === nothing ? zero(info) : sse, length(timepoints), sigma)
@@ -1034,6 +1064,17 @@ function conditional_standard_errors(betas, neural_network_parameters, models, t
     _, info, _, sse = sensitivities((neural = neural_network_parameters, conditional = betas),
                                     (models, timepoints, cpeptide_data); n_steps = n_steps)
     standard_errors(info, sse, length(timepoints), sigma)
+end
+# is every fitted conditional a minimum of SSEᵢ + pw (β - prior mean)²?  observed = curv + pw, expected = info + pw, their
+# ratio, and status :minimum, :not_a_minimum (observed ≤ 0) or :failed; pw = σ²/prior_Ω² (0 without a prior)
+function map_curvature(betas, neural_network_parameters, models, timepoints, cpeptide_data; sigma, prior_omega = nothing,
+                       n_steps = nothing)
+    _, curv, info, _, _ = curvatures((neural = neural_network_parameters, conditional = betas),
+                                     (models, timepoints, cpeptide_data); n_steps = n_steps)
+    pw = prior_omega === nothing ? 0.0 : (sigma / prior_omega)^2
+    observed, expected = curv .+ pw, info .+ pw
+    status = [isnan(o) ? :failed : o > 0 ? :minimum : :not_a_minimum for o in observed]
+    (observed = observed, expected = expected, ratio = observed ./ expected, status = status)
 end
 # standard normal quantile (Acklam's rational approximation, relative error 1.2e-9; no Distributions dependency)
 function normal_quantile(p)
@@ -1057,9 +1098,9 @@ function normal_quantile(p)
 end
 # Wald intervals βᵢ ∓ z·seᵢ, one (lower, upper) pair per subject as find_confidence_intervals returns for a profile
 function wald_confidence_intervals(betas, neural_network_parameters, models, timepoints, cpeptide_data;
-                                   sigma = nothing, level = 0.95, n_steps = nothing)
+                                   sigma = nothing, level = 0.95, n_steps = nothing, information = :expected)
     se = conditional_standard_errors(betas, neural_network_parameters, models, timepoints, cpeptide_data;
-                                     sigma = sigma, n_steps = n_steps)
+                                     sigma = sigma, n_steps = n_steps, information = information)
     z = normal_quantile(0.5 + level / 2)
     [(betas[i] - z * se[i], betas[i] + z * se[i]) for i in eachindex(se)]
 end
@@ -1093,6 +1134,12 @@ function suppression_sensitivities(p, (prob, individual_data, timepoints, λ); n
     c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
     set_params!(c, p.neural, p.theta)
     sensitivity(c)
+end
+# (sens2 [3 × T × N] = ∂²u/∂θᵢ² (state 1 exactly 0), curv, info, score, sse) with the loss's weights 1/scaleₛ
+function suppression_curvatures(p, (prob, individual_data, timepoints, λ); n_steps = nothing)
+    c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
+    set_params!(c, p.neural, p.theta)
+    curvature(c)
 end
 function suppression_loss_and_gradient!(G, p, (prob, individual_data, timepoints, λ))
     c = supp_population(prob, individual_data, timepoints, λ)
@@ -1247,11 +1294,20 @@ end
 # n_nodes-point Gauss-Hermite rule at every MAP (refine_conditional with penalty weight (σ/Ω)² from betas; nothing: an
 # 81-point scan first) with the Laplace scale σ / √(info + (σ/Ω)²); :importance: n_nodes device draws from that normal;
 # :grid: the trapezoid rule on n_nodes points over prior_mean ∓ grid_halfwidth Ω.  The likelihood follows the reference's
-# convention (no 2π constant); normalized = true adds -(T/2) log 2π per individual.  total = the sum in subject order
+# convention (no 2π constant); normalized = true adds -(T/2) log 2π per individual.  total = the sum in subject order.
+# :laplace is :quadrature with one node.  curvature = :observed: the scale is σ / √(curv + (σ/Ω)²) from one cude_curvature
+# call at the refined centres; where curv + (σ/Ω)² ≤ 0 the expected scale stays, and the result gains
+# curvature_fallback, the indices of those individuals
 function marginal_likelihood(betas, p_neural, individuals, network::Chain, σ, prior_mean, Ω; method = :quadrature,
                              n_nodes = 33, grid_halfwidth = 8.0, lower = -6.0, upper = 4.0, first_step = 0, seed = nothing,
-                             normalized = false, n_steps = nothing)
-    method in (:quadrature, :grid, :importance) || error("method must be :quadrature, :grid or :importance")
+                             normalized = false, n_steps = nothing, curvature = :expected)
+    method in (:quadrature, :grid, :importance, :laplace) ||
+        error("method must be :quadrature, :grid, :importance or :laplace")
+    curvature in (:expected, :observed) || error("curvature must be :expected or :observed")
+    if method == :laplace
+        method, n_nodes = :quadrature, 1
+    end
+    fallback = Int[]
     c = individuals_population(individuals, network; n_steps = n_steps)
     set_params!(c, p_neural, nothing)
     if method == :grid
@@ -1264,6 +1320,17 @@ function marginal_likelihood(betas, p_neural, individuals, network::Chain, σ, p
                                      start = betas === nothing ? nothing : Vector{Float64}(vec(betas)), penalty_weight = pw,
                                      penalty_center = prior_mean)
         scale = σ ./ sqrt.(info .+ pw)
+        if curvature == :observed
+            set_params!(c, nothing, center)
+            curv = CUDEHip.curvature(c; want_sens2 = false)[2]
+            for i in eachindex(curv)
+                if curv[i] + pw > 0
+                    scale[i] = σ / sqrt(curv[i] + pw)
+                else
+                    push!(fallback, i)
+                end
+            end
+        end
         if method == :quadrature
             z, a = gauss_hermite_rule(n_nodes)
             r = marginal_likelihood(c, σ, prior_mean, Ω; nodes = z, log_weights = a, center = center, scale = scale)
@@ -1274,8 +1341,9 @@ function marginal_likelihood(betas, p_neural, individuals, network::Chain, σ, p
         end
     end
     logml = normalized ? r[1] .- 0.5 * c.T * log(2π) : r[1]
-    (logml = logml, total = foldl(+, logml), post_mean = r[2], post_var = r[3], post_sse = r[4], ess = r[5], n_bad = r[6],
-     center = center, scale = scale)
+    out = (logml = logml, total = foldl(+, logml), post_mean = r[2], post_var = r[3], post_sse = r[4], ess = r[5],
+           n_bad = r[6], center = center, scale = scale)
+    curvature == :observed ? merge(out, (curvature_fallback = fallback,)) : out
 end
 
 # AIC and BIC from a population's marginal log-likelihood: bic penalises with the count of all observations, bic_subjects

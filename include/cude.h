@@ -201,6 +201,31 @@ int32_t cude_simulate(cude_ctx* ctx, int32_t n_times, const double* times, doubl
  * subjects); the others are unaffected.  CUDE_ERR_UNSUPPORTED for a network on the fallback kernel (cude_set_network). */
 int32_t cude_sensitivity(cude_ctx* ctx, double* sens, double* info, double* score, double* sse);
 
+/* Exact per-subject curvature: the SECOND derivative of every subject's trajectory with respect to its own conditional
+ * parameter, by an order-2 forward-mode solve (u, du/dcond and d2u/dcond2 carried together through network, step and
+ * interpolant), and with it the true curvature of the subject's objective, of which cude_sensitivity's info is the
+ * Gauss-Newton part -- what ForwardDiff.hessian of the per-subject objective of src/parameter-estimation.jl:165,370 /
+ * suppression/src/suppression_model.jl:155 gives.  It is the exact second derivative of the discrete map (every stage,
+ * the FSAL carry, the dense-output weights), not a discretisation of a second-order sensitivity equation.  All five
+ * outputs are optional, at least one must be given; the context's current parameters are used and left untouched.
+ *   1. sens2 [n_state x T x N] column-major (cude_forward's traj layout): d^2 u_s(t_j) / d cond_i^2 at the data's time
+ *      points.  Column t_0 is exactly 0 (u0 depends on no parameter); suppression state 1 is exactly 0.
+ *   2. curv [N] = sum over the observed outputs of w^2 [(d yhat / d cond)^2 + (yhat - y) d^2 yhat / d cond^2]
+ *      = (1/2) d^2 SSE_i / d cond_i^2, in cude_sensitivity's weighting: c-peptide models state 1 with w = 1, suppression
+ *      model all three states with w = 1 / scale_s.  The observed information of cond_i is curv / sigma^2; it may be <= 0
+ *      (a saddle or a maximum of the objective, which info >= 0 can never show).
+ *   3. info, score and sse are as cude_sensitivity defines them.  Always curv - info = sum w^2 (yhat - y) d^2 yhat / d cond^2.
+ *   4. Derivatives are with respect to the parameter AS STORED: log space includes the chain factor at both orders
+ *      (d^2/d beta^2 = k^2 d^2/dk^2 + k d/dk), CUDE_COND_RAW takes k itself.  Adaptive mode: step control reads the
+ *      solve's own error estimate only, so the accepted steps are cude_forward's and the result is the second derivative
+ *      of the accepted-step map (cude_sensitivity's convention); the steps are left where cude_adaptive_steps reads them.
+ *   5. Failures are cude_sensitivity's: a subject with a non-finite input or a failed adaptive solve gets NaN in all its
+ *      outputs and is counted by cude_n_failed (this rank's subjects); the others are unaffected.
+ *   6. CUDE_ERR_UNSUPPORTED for a network on the fallback kernel (cude_set_network) and for a general-activation network
+ *      in adaptive mode; CUDE_ERR_STATE without population or parameters, and under stream capture; CUDE_ERR_ARG with no
+ *      output.  A sharded population needs no exchange: every rank's subjects are its own. */
+int32_t cude_curvature(cude_ctx* ctx, double* sens2, double* curv, double* info, double* score, double* sse);
+
 /* Multi-start screening: forward-only loss of n_sets candidate parameter sets over the resident
  * population in one launch (first phase of `train`, src/parameter-estimation.jl:351-366;
  * fit_suppression_model suppression_model.jl:135; c-peptide/06-saem.jl:41-42).
