@@ -1,6 +1,6 @@
 // libcude_hip.so -- the entry points that batch launches: dense output and predictive bands, conditional sets, marginal
 // likelihoods, subject scores, network information, sensitivities, multi-start evaluation and screening, likelihood
-// profiles and their intervals, per-subject fits.  Each is its own argument checks, chunking, small kernels and copies
+// profiles and their intervals, per-subject fits and their parametric bootstrap.  Each is its own argument checks, chunking, small kernels and copies
 // around the launches of cude_launch.hip, in chunks sized by cude_select.hip's sets_per_launch.
 #include "cude_ctx.h"
 
@@ -38,6 +38,41 @@ int32_t check_output_times(const cude_ctx* c, int32_t n_times, const double* tim
             return fail(CUDE_ERR_ARG, "output times must lie inside the time span of the population");
         if (i > 0 && !(times[i] >= times[i - 1])) return fail(CUDE_ERR_ARG, "output times must be non-decreasing");
     }
+    return CUDE_OK;
+}
+
+// The stepped form of the per-subject fits (cude_refine_conditional; one replicate of cude_bootstrap_conditional): per
+// evaluation a tangent launch at the trial points and the rule's update; every round is queued, the subjects that have
+// stopped keep their state (and are solved along at their last trial point).  obs_ov: launch_tangent's.
+hipError_t refine_stepped(cude_ctx* c, const cude::RefineCfg& k, const cude::RefineArrays& r, double* sse_t, double* score_t,
+                          double* info_t, const double* obs_ov) {
+    hipError_t le = cude::launch_refine_step(0, k, r, c->stream);
+    cude::SensOut out;
+    out.info = info_t;
+    out.score = score_t;
+    for (int it = 0; it < k.max_evals && le == hipSuccess; it++) {
+        le = launch_tangent(c, r.xt, sse_t, out, false, obs_ov);
+        if (le == hipSuccess) le = cude::launch_refine_step(1, k, r, c->stream);
+    }
+    // (adaptive mode: nothing of these solves is on the gradient's tape -- cude_adaptive_steps refuses afterwards)
+    note_adaptive_launch(c, false);
+    return le;
+}
+
+// the search state of the fits in the context's scratch (13 rows of doubles, 2 of int32); x0 is the caller's
+int32_t refine_state(cude_ctx* c, cude::RefineArrays& r, double** sse_t, double** score_t, double** info_t) {
+    const int64_t N = c->N;
+    HIP_TRY(c->refine_buf.reserve((size_t)13 * N));       // x0, x, F, sse, info, g, lam, xp, gp, xt, sse_t, score_t, info_t
+    HIP_TRY(c->refine_ibuf.reserve((size_t)2 * N));       // evals, status
+    double* q = c->refine_buf.p;
+    r.N = N;
+    r.x = q + N; r.F = q + 2 * N; r.sse = q + 3 * N; r.info = q + 4 * N;
+    r.g = q + 5 * N; r.lam = q + 6 * N; r.xp = q + 7 * N; r.gp = q + 8 * N; r.xt = q + 9 * N;
+    *sse_t = q + 10 * N;
+    *score_t = q + 11 * N;
+    *info_t = q + 12 * N;
+    r.sse_t = *sse_t; r.score_t = *score_t; r.info_t = *info_t;
+    r.evals = c->refine_ibuf.p; r.status = c->refine_ibuf.p + N;
     return CUDE_OK;
 }
 }  // namespace
@@ -1047,29 +1082,18 @@ int32_t cude_refine_conditional(cude_ctx* c, const double* x0, double lower, dou
     if (c->capturing) return fail(CUDE_ERR_STATE, "cude_refine_conditional under stream capture");
     const bool cpep = is_cpep(c);
     const int64_t N = c->N;
-    DevBuf<double>& buf = c->refine_buf;                  // x0, x, F, sse, info, g, lam, xp, gp, xt, sse_t, score_t, info_t
-    DevBuf<int32_t>& ibuf = c->refine_ibuf;               // evals, status
-    HIP_TRY(buf.reserve((size_t)13 * N));
-    HIP_TRY(ibuf.reserve((size_t)2 * N));
     cude::RefineCfg k{};
     k.lower = lower; k.upper = upper; k.xtol = xtol; k.max_step = max_step;
     k.pw = penalty_weight; k.pc = penalty_center; k.max_evals = max_evals;
     cude::RefineArrays r{};
-    r.N = N;
-    double* q = buf.p;
+    double *sse_t = nullptr, *score_t = nullptr, *info_t = nullptr;
+    if ((rc = refine_state(c, r, &sse_t, &score_t, &info_t))) return rc;
     if (x0) {
-        HIP_TRY(push(c, q, x0, N));
-        r.x0 = q;
+        HIP_TRY(push(c, c->refine_buf.p, x0, N));
+        r.x0 = c->refine_buf.p;
     } else {
         r.x0 = c->cond.p;
     }
-    r.x = q + N; r.F = q + 2 * N; r.sse = q + 3 * N; r.info = q + 4 * N;
-    r.g = q + 5 * N; r.lam = q + 6 * N; r.xp = q + 7 * N; r.gp = q + 8 * N; r.xt = q + 9 * N;
-    double* sse_t = q + 10 * N;
-    double* score_t = q + 11 * N;
-    double* info_t = q + 12 * N;
-    r.sse_t = sse_t; r.score_t = score_t; r.info_t = info_t;
-    r.evals = ibuf.p; r.status = ibuf.p + N;
     hipError_t le = hipSuccess;
     if (!adaptive(c) && c->opt.refine_fused) {
         // the whole iteration of every subject in ONE launch
@@ -1083,18 +1107,7 @@ int32_t cude_refine_conditional(cude_ctx* c, const double* x0, double lower, dou
             le = cude::launch_supp_refine(c->net, a, k, r, c->stream);
         }
     } else {
-        // per evaluation a tangent launch at the trial points and the rule's update; every round is queued, the subjects that
-        // have stopped keep their state (and are solved along at their last trial point)
-        HIP_TRY(cude::launch_refine_step(0, k, r, c->stream));
-        cude::SensOut out;
-        out.info = info_t;
-        out.score = score_t;
-        for (int it = 0; it < max_evals && le == hipSuccess; it++) {
-            le = launch_tangent(c, r.xt, sse_t, out, false);
-            if (le == hipSuccess) le = cude::launch_refine_step(1, k, r, c->stream);
-        }
-        // (adaptive mode: nothing of these solves is on the gradient's tape -- cude_adaptive_steps refuses afterwards)
-        note_adaptive_launch(c, false);
+        le = refine_stepped(c, k, r, sse_t, score_t, info_t, nullptr);
     }
     if (le == hipErrorInvalidValue)
         return fail(CUDE_ERR_UNSUPPORTED, "cude_refine_conditional: no tangent kernel compiled for this network shape / model");
@@ -1117,6 +1130,184 @@ int32_t cude_refine_conditional(cude_ctx* c, const double* x0, double lower, dou
     for (int64_t i = 0; i < N; i++) n_failed += status[(size_t)i] == CUDE_REFINE_FAILED;
     c->last_failed = n_failed;
     if (status_out) std::memcpy(status_out, status.data(), (size_t)N * sizeof(int32_t));
+    return CUDE_OK;
+}
+
+int32_t cude_bootstrap_conditional(cude_ctx* c, const double* center, const double* sigma, int64_t first_rep, int32_t n_reps,
+                                   const double* noise, double lower, double upper, int32_t max_evals, double xtol,
+                                   double max_step, double penalty_weight, double penalty_center, int32_t n_ranks,
+                                   const int32_t* ranks, double* order_out, double* mean_out, double* sd_out,
+                                   int32_t* n_used_out, double* reps_out, int32_t* status_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (!center && !c->have_cond) return fail(CUDE_ERR_STATE, "no centre: conditional parameters not set and center is null");
+    if (!(lower < upper) || !std::isfinite(lower) || !std::isfinite(upper)) return fail(CUDE_ERR_ARG, "need finite lower < upper");
+    if (max_evals < 1 || !(xtol > 0) || !(max_step > 0) || !(penalty_weight >= 0) || !std::isfinite(penalty_weight) ||
+        !std::isfinite(penalty_center))
+        return fail(CUDE_ERR_ARG, "need max_evals >= 1, xtol > 0, max_step > 0, finite penalty_weight >= 0");
+    if (n_reps < 1 || n_reps > cude::kPredMaxSets) return fail(CUDE_ERR_ARG, "need 1 <= n_reps <= 4096");
+    if (first_rep < 0 || first_rep > cude::kRngMaxReplicate - n_reps) return fail(CUDE_ERR_ARG, "need 0 <= first_rep, first_rep + n_reps <= 2^47");
+    if (n_ranks < 0 || n_ranks > cude::kPredMaxRanks) return fail(CUDE_ERR_ARG, "need 0 <= n_ranks <= 16");
+    if ((n_ranks > 0 && (!ranks || !order_out)) || (n_ranks == 0 && order_out))
+        return fail(CUDE_ERR_ARG, "need order_out with n_ranks > 0 ranks, and only then");
+    if (!order_out && !mean_out && !sd_out && !n_used_out && !reps_out && !status_out) return fail(CUDE_ERR_ARG, "no output requested");
+    for (int32_t r = 0; r < n_ranks; r++)
+        if (ranks[r] < 0 || ranks[r] >= n_reps || (r > 0 && ranks[r] <= ranks[r - 1]))
+            return fail(CUDE_ERR_ARG, "ranks must be strictly increasing inside [0, n_reps)");
+    if (!sigma) return fail(CUDE_ERR_ARG, "null sigma");
+    const int64_t N = c->N, nb = c->nblocks;
+    for (int64_t i = 0; i < N; i++)
+        if (!(sigma[i] >= 0) || !std::isfinite(sigma[i])) return fail(CUDE_ERR_ARG, "sigma must be finite and >= 0");
+    if (c->net.generic())
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_bootstrap_conditional: the network of this context runs on the fallback kernel "
+                                          "(cude_set_network), which has no tangent-linear solve");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_bootstrap_conditional under stream capture");
+    const bool cpep = is_cpep(c);
+    const int T = c->T, n_states = cpep ? 1 : 3, rows = n_states * T;
+    const bool fused = !adaptive(c) && c->opt.refine_fused;
+    // Replicates per launch: ~256 MB of replicate observations ([rows][N] each).  Subjects per pass: whole workgroups, as many
+    // as ~1 GB of replicate results (a double and an int32 per replicate and subject) allow.
+    const int64_t chunk = sets_per_launch(n_reps, 65535, 256e6, 8.0 * rows * (double)N, c->opt.bootstrap_chunk);
+    int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)(1e9 / (12.0 * n_reps * cude::kBlock))));
+    if (c->opt.bootstrap_subjects > 0)
+        blocks = std::min<int64_t>(nb, ((int64_t)c->opt.bootstrap_subjects + cude::kBlock - 1) / cude::kBlock);
+    const int64_t sub_max = std::min<int64_t>(N, blocks * cude::kBlock);
+    DevBuf<double> d_in, d_slab, d_reps, d_sum;
+    DevBuf<int32_t> d_status, d_int;
+    HIP_TRY(d_in.resize((size_t)3 * N));                  // centre, sigma, the SSE of the centre's solve (not reported)
+    HIP_TRY(d_slab.resize((size_t)chunk * rows * N));
+    HIP_TRY(d_reps.resize((size_t)n_reps * sub_max));
+    HIP_TRY(d_status.resize((size_t)n_reps * sub_max));
+    HIP_TRY(d_sum.resize((size_t)(n_ranks + 2) * sub_max));        // order [n_ranks][sub_max], mean, sd
+    HIP_TRY(d_int.resize((size_t)sub_max + (size_t)std::max(n_ranks, 1)));      // n_used, ranks
+    double* const d_center = d_in.p;
+    double* const d_sigma = d_in.p + N;
+    double* const d_order = d_sum.p;
+    double* const d_mean = d_sum.p + (size_t)n_ranks * sub_max;
+    double* const d_sd = d_mean + sub_max;
+    int32_t* const d_used = d_int.p;
+    int32_t* const d_ranks = d_int.p + sub_max;
+    if (center) HIP_TRY(push(c, d_center, center, N));
+    else HIP_TRY(hipMemcpyAsync(d_center, c->cond.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(push(c, d_sigma, sigma, N));
+    if (n_ranks > 0) HIP_TRY(push(c, d_ranks, ranks, n_ranks));
+    // rule 1: cude_forward's trajectory at the centre
+    HIP_TRY(c->traj.resize((size_t)c->cfg.n_state * T * N));
+    if ((rc = run_ensemble(c, false, c->traj.p, true, d_center, d_in.p + 2 * N))) return rc;
+    if (adaptive(c)) c->have_tape = false;
+    cude::BootstrapGenArgs g{};
+    g.N = N; g.T = T; g.n_states = n_states; g.traj_states = c->cfg.n_state;
+    for (int s = 0; s < 3; s++) g.scale[s] = cpep ? 1.0 : c->scale[s];
+    g.traj = c->traj.p; g.sigma = d_sigma; g.pop = cpep ? c->obs.p : c->data.p;
+    g.slab = d_slab.p; g.from_noise = noise ? 1 : 0;
+    g.seed = c->rng_seed; g.subject_offset = c->rng_offset;
+    cude::RefineCfg k{};
+    k.lower = lower; k.upper = upper; k.xtol = xtol; k.max_step = max_step;
+    k.pw = penalty_weight; k.pc = penalty_center; k.max_evals = max_evals;
+    cude::RefineArrays r{};
+    double *sse_t = nullptr, *score_t = nullptr, *info_t = nullptr;
+    if (fused) r.N = N;
+    else if ((rc = refine_state(c, r, &sse_t, &score_t, &info_t))) return rc;
+    r.x0 = d_center;
+    std::vector<int32_t> used((size_t)N);
+    const size_t pitch_host = (size_t)N * sizeof(double), pitch_dev = (size_t)sub_max * sizeof(double);
+    for (int64_t b0 = 0; b0 < nb; b0 += blocks) {
+        const int64_t bn = std::min<int64_t>(blocks, nb - b0);
+        const int64_t s0 = b0 * cude::kBlock, sn = std::min<int64_t>(N, (b0 + bn) * cude::kBlock) - s0;
+        g.subj0 = s0; g.n_subj = sn;
+        for (int64_t k0 = 0; k0 < n_reps; k0 += chunk) {
+            const int64_t kn = std::min<int64_t>(chunk, n_reps - k0);
+            g.n_reps = (int32_t)kn; g.first_rep = first_rep + k0;
+            // the caller's noise of these subjects goes into the slab itself and is turned into observations in place
+            if (noise)
+                HIP_TRY(hipMemcpy2DAsync(d_slab.p + s0, pitch_host, noise + (size_t)k0 * rows * N + s0, pitch_host,
+                                         (size_t)sn * sizeof(double), (size_t)kn * rows, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(cude::launch_bootstrap_generate(g, c->stream));
+            hipError_t le = hipSuccess;
+            if (fused) {
+                // every fit of the chunk in ONE launch: workgroup (x, y) = subjects 64 (b0 + x) ... of replicate k0 + y
+                cude::RefineReps p{};
+                p.slab = d_slab.p; p.slab_stride = (int64_t)rows * N; p.rep_stride = sub_max;
+                p.blk_first = b0; p.blk_count = bn; p.n_reps = (int32_t)kn;
+                r.x = d_reps.p + k0 * sub_max - s0;
+                r.status = d_status.p + k0 * sub_max - s0;
+                if (cpep) {
+                    cude::CpepArgs a = cpep_args(c);
+                    a.nn = c->nn.p;
+                    le = cude::launch_cpep_refine(c->net, c->cfg.n_state, a, k, r, c->stream, &p);
+                } else {
+                    cude::SuppArgs a = supp_args(c);
+                    a.nn = c->nn.p;
+                    le = cude::launch_supp_refine(c->net, a, k, r, c->stream, &p);
+                }
+            } else {
+                // the stepped form, one replicate at a time over the whole population: max_evals tangent launches each
+                for (int64_t b = 0; b < kn && le == hipSuccess; b++) {
+                    le = refine_stepped(c, k, r, sse_t, score_t, info_t, d_slab.p + b * rows * N);
+                    if (le != hipSuccess) break;
+                    HIP_TRY(hipMemcpyAsync(d_reps.p + (k0 + b) * sub_max, r.x + s0, (size_t)sn * sizeof(double),
+                                           hipMemcpyDeviceToDevice, c->stream));
+                    HIP_TRY(hipMemcpyAsync(d_status.p + (k0 + b) * sub_max, r.status + s0, (size_t)sn * sizeof(int32_t),
+                                           hipMemcpyDeviceToDevice, c->stream));
+                }
+            }
+            if (le == hipErrorInvalidValue)
+                return fail(CUDE_ERR_UNSUPPORTED, "cude_bootstrap_conditional: no tangent kernel compiled for this network shape / model");
+            HIP_TRY(le);
+        }
+        // rule 5, over all replicates of these subjects
+        cude::BootstrapReduceArgs ra{};
+        ra.reps = d_reps.p; ra.status = d_status.p; ra.stride = sub_max; ra.n_subj = sn;
+        ra.K = n_reps; ra.n_ranks = n_ranks;
+        ra.order = n_ranks > 0 ? d_order : nullptr; ra.out_stride = sub_max;
+        ra.mean = d_mean; ra.sd = d_sd; ra.n_used = d_used;
+        HIP_TRY(cude::launch_bootstrap_reduce(ra, d_ranks, c->stream));
+        if (order_out)
+            HIP_TRY(hipMemcpy2DAsync(order_out + s0, pitch_host, d_order, pitch_dev, (size_t)sn * sizeof(double), (size_t)n_ranks,
+                                     hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(fetch(c, mean_out ? mean_out + s0 : nullptr, d_mean, sn));
+        HIP_TRY(fetch(c, sd_out ? sd_out + s0 : nullptr, d_sd, sn));
+        HIP_TRY(fetch(c, used.data() + s0, d_used, sn));
+        if (reps_out)
+            HIP_TRY(hipMemcpy2DAsync(reps_out + s0, pitch_host, d_reps.p, pitch_dev, (size_t)sn * sizeof(double), (size_t)n_reps,
+                                     hipMemcpyDeviceToHost, c->stream));
+        if (status_out)
+            HIP_TRY(hipMemcpy2DAsync(status_out + s0, (size_t)N * sizeof(int32_t), d_status.p, (size_t)sub_max * sizeof(int32_t),
+                                     (size_t)sn * sizeof(int32_t), (size_t)n_reps, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));         // the result tables are the next pass's too
+    }
+    int64_t failed = 0;
+    for (int64_t i = 0; i < N; i++) failed += used[(size_t)i] < n_reps;
+    c->last_failed = failed;
+    if (n_used_out) std::memcpy(n_used_out, used.data(), (size_t)N * sizeof(int32_t));
+    return CUDE_OK;
+}
+
+int32_t cude_bootstrap_noise(cude_ctx* c, int64_t first_rep, int32_t n_reps, double* noise_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (n_reps < 1 || n_reps > cude::kPredMaxSets) return fail(CUDE_ERR_ARG, "need 1 <= n_reps <= 4096");
+    if (first_rep < 0 || first_rep > cude::kRngMaxReplicate - n_reps) return fail(CUDE_ERR_ARG, "need 0 <= first_rep, first_rep + n_reps <= 2^47");
+    if (!noise_out) return fail(CUDE_ERR_ARG, "null output");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_bootstrap_noise under stream capture");
+    const int64_t N = c->N;
+    const int T = c->T, n_states = is_cpep(c) ? 1 : 3, rows = n_states * T;
+    const int64_t chunk = sets_per_launch(n_reps, 65535, 256e6, 8.0 * rows * (double)N, c->opt.bootstrap_chunk);
+    DevBuf<double> d_eps;
+    HIP_TRY(d_eps.resize((size_t)chunk * rows * N));
+    cude::BootstrapGenArgs g{};
+    g.N = N; g.subj0 = 0; g.n_subj = N; g.T = T; g.n_states = n_states;
+    g.seed = c->rng_seed; g.subject_offset = c->rng_offset;
+    for (int64_t k0 = 0; k0 < n_reps; k0 += chunk) {
+        const int64_t kn = std::min<int64_t>(chunk, n_reps - k0);
+        g.n_reps = (int32_t)kn; g.first_rep = first_rep + k0;
+        HIP_TRY(cude::launch_bootstrap_noise(g, d_eps.p, c->stream));
+        HIP_TRY(fetch(c, noise_out + (size_t)k0 * rows * N, d_eps.p, (size_t)kn * rows * N));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     return CUDE_OK;
 }
 

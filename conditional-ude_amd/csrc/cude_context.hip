@@ -213,6 +213,8 @@ const OptionEntry kOptions[] = {
     {"profile_chunk", "CUDE_PROFILE_CHUNK", &Options::profile_chunk, false, false},
     {"predictive_subjects", "CUDE_PREDICTIVE_SUBJECTS", &Options::predictive_subjects, false, false},
     {"predictive_times", "CUDE_PREDICTIVE_TIMES", &Options::predictive_times, false, false},
+    {"bootstrap_chunk", "CUDE_BOOTSTRAP_CHUNK", &Options::bootstrap_chunk, false, false},
+    {"bootstrap_subjects", "CUDE_BOOTSTRAP_SUBJECTS", &Options::bootstrap_subjects, false, false},
 };
 }  // namespace
 

@@ -99,6 +99,10 @@ struct Options {
                                 //   rounded up to whole workgroups of 64 (0 = as many as ~1 GB of sample trajectories allow)
     int predictive_times = 0;   // "predictive_times" / CUDE_PREDICTIVE_TIMES: its output times per launch (0 = all of them unless 64
                                 //   subjects alone exceed that budget); tests force several launches in either dimension with them
+    int bootstrap_chunk = 0;    // "bootstrap_chunk" / CUDE_BOOTSTRAP_CHUNK: replicates per launch of cude_bootstrap_conditional (0 = as many
+                                //   as ~256 MB of replicate observations allow)
+    int bootstrap_subjects = 0; // "bootstrap_subjects" / CUDE_BOOTSTRAP_SUBJECTS: its subjects per pass, rounded up to whole workgroups of
+                                //   64 (0 = as many as ~1 GB of replicate results allow); tests force either split with them
     // ("hidden_activation" = tanh | relu | sigmoid, "output_activation" = softplus | identity: kept in cude_ctx::net)
     // ---- ablation
     int mixed = 1;              // CUDE_NO_MIXED
@@ -370,7 +374,9 @@ struct SetsRows {
 };
 int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t stride_nn, const double* cond,
                          int64_t stride_cond, double* g_cond, double* out, const SetsRows* rows = nullptr);
-hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, bool keep_tape);
+// obs_ov: observations to read instead of the population's, in its layout (obs [T][N] / data [3][T][N])
+hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, bool keep_tape,
+                          const double* obs_ov = nullptr);
 // ... one order-2 solve (cude_curv.hip): `out.sens` is not written, `out2` holds the second-order outputs
 hipError_t launch_tangent2(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, const cude::CurvOut& out2,
                            bool keep_tape);

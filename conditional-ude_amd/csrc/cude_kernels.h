@@ -522,12 +522,50 @@ struct RefineArrays {
     double* g; double* lam; double* xp; double* gp; double* xt;      // stepped form: half gradient, damping, secant pair, trial
     const double* sse_t; const double* score_t; const double* info_t;   // stepped form: the evaluation at xt
 };
-// fused form (fixed-step mode): hipErrorInvalidValue when no kernel is compiled for the shape
-hipError_t launch_cpep_refine(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
-hipError_t launch_supp_refine(const NetShape& net, const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
+// The fused form with a replicate dimension (cude_bootstrap_conditional): a grid of blk_count x n_reps workgroups, (x, y)
+// fitting subjects 64 (blk_first + x) ... of replicate y on the observations slab + y * slab_stride (the population's own
+// layout: obs [T][N] / data [3][T][N]) from RefineArrays::x0, and storing ONLY x and status, at [y * rep_stride + subject].
+// A kernel family of its own beside the one-replicate kernels: with these fields in RefineArrays the one-replicate kernels
+// compiled to other register counts and spills (profiles/bootstrap.txt), and they are held to what they were.
+struct RefineReps {
+    const double* slab; int64_t slab_stride, rep_stride, blk_first, blk_count;
+    int32_t n_reps;
+};
+// fused form (fixed-step mode): hipErrorInvalidValue when no kernel is compiled for the shape.  reps: the replicate family.
+hipError_t launch_cpep_refine(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s,
+                              const RefineReps* reps = nullptr);
+hipError_t launch_supp_refine(const NetShape& net, const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s,
+                              const RefineReps* reps = nullptr);
 // phase 0 = clamp the starts, 1 = the rule's update behind an evaluation at xt (both: stepped form); 2 = objective at the
 // result from the SSE in r.sse (either form)
 hipError_t launch_refine_step(int phase, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
+// Parametric bootstrap of the per-subject fits (cude_bootstrap_conditional, cude_bootstrap.hip; the numbered rules in
+// include/cude.h).  Replicate data of subjects [subj0, subj0 + n_subj): slab[b][r][i] = yhat[r, i] + sigma[i] * s_r * eps, eps
+// = what the slab held (host noise, uploaded in place) or the Philox draw of (subject_offset + i, first_rep + b, r); rows of
+// t_0 are copied from `pop`.
+constexpr int64_t kRngMaxReplicate = (int64_t)1 << 47;     // replicate indices the draws' counter holds (cude_rng.h)
+struct BootstrapGenArgs {
+    int64_t N, subj0, n_subj;
+    int32_t T, n_states, traj_states;             // rows r = s * T + t, s < n_states; yhat(s, t, i) = traj[s + traj_states (t + T i)]
+    double scale[3];                              // s_r of state s
+    const double* traj; const double* sigma; const double* pop;     // pop: [n_states * T][N], the slab's layout
+    double* slab;                                 // [n_reps][n_states * T][N]
+    int32_t n_reps, from_noise;                   // from_noise: eps is read from the slab; 0: drawn
+    uint64_t seed; int64_t subject_offset, first_rep;
+};
+hipError_t launch_bootstrap_generate(const BootstrapGenArgs& a, hipStream_t s);
+// eps alone: out[b][r][i] (t_0 rows +0.0), the draws launch_bootstrap_generate uses
+hipError_t launch_bootstrap_noise(const BootstrapGenArgs& a, double* out, hipStream_t s);
+// Rule 5 over reps / status [K][stride] (subject i of the launch at column i, n_subj of them): per subject n_used, the
+// sequential mean, the two-pass sd and the order statistics `ranks_dev` of its non-FAILED estimates.  Outputs at the
+// subject's index of the launch: order [n_ranks][out_stride], mean, sd, n_used [.] (order null with n_ranks == 0).
+struct BootstrapReduceArgs {
+    const double* reps; const int32_t* status; int64_t stride, n_subj;
+    int32_t K, n_ranks;
+    double* order; int64_t out_stride;
+    double* mean; double* sd; int32_t* n_used;
+};
+hipError_t launch_bootstrap_reduce(const BootstrapReduceArgs& a, const int32_t* ranks_dev, hipStream_t s);
 // per-subject profile-likelihood intervals (cude_profile_intervals, cude_common.hip): the scan's running state, the ends'
 // brackets and the CUDE_CI_* bits of include/cude.h; all arrays [N] unless noted
 constexpr int kProfileWaves = 4;                  // waves of a reduction workgroup: the set dimension is split over them

@@ -549,7 +549,9 @@ int32_t eval_sets_device(cude_ctx* c, int64_t n_sets, const double* nn, int64_t 
 
 // Queues one tangent-linear solve of the context's model at `cond` on its stream: the per-subject SSE goes to `sse`, the
 // sums of `out` next to it, [sum SSE, failures] to c->partials.  keep_tape = false: an adaptive solve records no steps.
-hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, bool keep_tape) {
+// obs_ov: the residuals are taken against these observations (the population's layout) instead of the population's.
+hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cude::SensOut& out, bool keep_tape,
+                          const double* obs_ov) {
     const auto fill = [&](auto& a) {
         a.cond = cond; a.nn = c->nn.p; a.sse = sse; a.partials = c->partials.p;
         if (!keep_tape) a.tape = nullptr;
@@ -559,11 +561,13 @@ hipError_t launch_tangent(cude_ctx* c, const double* cond, double* sse, const cu
         cude::CpepSensArgs a{};
         static_cast<cude::CpepArgs&>(a) = cpep_args(c);
         fill(a);
+        if (obs_ov) a.obs = obs_ov;
         return cude::launch_cpep_sens(c->net, c->cfg.n_state, a, c->stream);
     }
     cude::SuppSensArgs a{};
     static_cast<cude::SuppArgs&>(a) = supp_args(c);
     fill(a);
+    if (obs_ov) a.data = obs_ov;
     return cude::launch_supp_sens(c->net, a, c->stream);
 }
 

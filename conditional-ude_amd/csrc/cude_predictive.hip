@@ -20,14 +20,14 @@
 #include <hip/hip_runtime.h>
 
 #include "cude_kernels.h"
+#include "cude_tilesort.h"
 
 namespace cude {
 
 namespace {
-constexpr int kPredThreads = 256;
-constexpr int kPredTileDoubles = 8192;     // 64 KiB
-constexpr int kPredMaxCols = 64;
-constexpr int kPredPairs = kPredTileDoubles / 2 / kPredThreads;     // compare-exchanges per thread and pass of the network
+constexpr int kPredThreads = kTileSortThreads;
+constexpr int kPredTileDoubles = kTileSortDoubles;     // 64 KiB
+constexpr int kPredMaxCols = kTileSortMaxCols;
 
 __global__ __launch_bounds__(kPredThreads) void predictive_select_kernel(PredictiveArgs a, const int32_t* __restrict__ ranks,
                                                                          int lgC, int Kp) {
@@ -65,36 +65,7 @@ __global__ __launch_bounds__(kPredThreads) void predictive_select_kernel(Predict
         s_bad[tid] = bad ? 1 : 0;
     }
     if (a.n_ranks == 0) return;
-    // ---- bitonic network, ascending; pair p of column cc compares elements lo < hi = lo + j
-    const int n_pair = n_el >> 1;
-    for (int k = 2; k <= Kp; k <<= 1) {
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            __syncthreads();
-            // a pass's pairs are disjoint: all of a thread's reads are requested before its first exchange is written, so
-            // the pass waits for one LDS round trip, not for one per pair
-            int ia[kPredPairs], ib[kPredPairs];
-            double x[kPredPairs], y[kPredPairs];
-#pragma unroll
-            for (int u = 0; u < kPredPairs; u++) {
-                const int idx = tid + u * kPredThreads;
-                const int cc = idx & (C - 1), p = idx >> lgC;
-                const int lo = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                const bool up = (lo & k) == 0;
-                ia[u] = (lo << lgC) + cc;
-                ib[u] = ((lo | j) << lgC) + cc;
-                if (idx < n_pair) {
-                    x[u] = s_v[up ? ia[u] : ib[u]];      // ascending runs keep (x, y) in place order, descending ones swapped:
-                    y[u] = s_v[up ? ib[u] : ia[u]];      // one test x > y for both
-                    if (!up) { const int t = ia[u]; ia[u] = ib[u]; ib[u] = t; }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < kPredPairs; u++) {
-                if (tid + u * kPredThreads < n_pair && x[u] > y[u]) { s_v[ia[u]] = y[u]; s_v[ib[u]] = x[u]; }
-            }
-        }
-    }
-    __syncthreads();
+    tile_sort_ascending(s_v, lgC, Kp, tid);      // (cude_tilesort.h)
     for (int idx = tid; idx < a.n_ranks << lgC; idx += kPredThreads) {
         const int r = idx % a.n_ranks, cc = idx / a.n_ranks;
         const int64_t q = q0 + cc;
@@ -115,13 +86,7 @@ __global__ void predictive_count_kernel(int64_t N, int K, const uint8_t* __restr
 }  // namespace
 
 // LDS of one workgroup and the columns of its tile
-size_t predictive_lds_bytes(int K, int* tile_cols) {
-    int Kp = 1;
-    while (Kp < K) Kp <<= 1;
-    const int C = kPredTileDoubles / Kp < kPredMaxCols ? kPredTileDoubles / Kp : kPredMaxCols;
-    if (tile_cols) *tile_cols = C;
-    return sizeof(double) * (size_t)Kp * C;
-}
+size_t predictive_lds_bytes(int K, int* tile_cols) { return tile_sort_lds_bytes(K, tile_cols); }
 
 // ranks_dev: [n_ranks] on the device, validated by the caller
 hipError_t launch_predictive_select(const PredictiveArgs& a, const int32_t* ranks_dev, hipStream_t s) {

@@ -15,7 +15,9 @@
 //     (cude_tangent.h cpep_tan_sweep / supp_tan_sweep, here without the trajectory stores) at the trial point, and the
 //     outer loop leaves when no lane of the wave is still running (ballot).  Lanes that have
 //     stopped run along masked: refine_update returns at once for them, their state stays what it was.  (The host adds
-//     one forward launch at the returned points, whose SSE is the one reported: cude_launch.hip.)
+//     one forward launch at the returned points, whose SSE is the one reported: cude_launch.hip.)  A second family of
+//     these kernels carries a replicate dimension in the grid's y (RefineReps; cude_bootstrap_conditional): the same
+//     loads, sweep and rule on observations read from a replicate slab.
 //   * stepped (adaptive mode, or option "refine_fused" = 0): per evaluation one launch of the tangent solve at the trial
 //     points (launch_cpep_sens / launch_supp_sens) and one refine_step_kernel; the state lives in device arrays.
 //
@@ -30,8 +32,8 @@ namespace cude {
 #define CUDE_REFINE_PART 0
 #endif
 
-hipError_t launch_cpep_refine_part1(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
-hipError_t launch_cpep_refine_part2(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s);
+hipError_t launch_cpep_refine_part1(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps);
+hipError_t launch_cpep_refine_part2(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps);
 
 constexpr int kRefConverged = 0, kRefAtBound = 1, kRefMaxEvals = 2, kRefFlat = 3, kRefFailed = 4;   // CUDE_REFINE_*
 constexpr double kRefLambda0 = 1e-3, kRefLambdaMin = 1e-12;
@@ -105,6 +107,12 @@ __device__ __forceinline__ void refine_store(const RefineArrays& r, int64_t i, c
     r.status[i] = s.status == kRefineRunning ? kRefMaxEvals : s.status;
 }
 
+// a replicate's fit (RefineReps): the point and the status alone, at q = replicate * rep_stride + subject
+__device__ __forceinline__ void refine_store_rep(const RefineArrays& r, int64_t q, const RefineLane& s) {
+    r.x[q] = s.x;
+    r.status[q] = s.status == kRefineRunning ? kRefMaxEvals : s.status;
+}
+
 #if CUDE_REFINE_PART != 3
 // ---------------------------------------------------------------------------------- c-peptide models, fused
 // Net: Mlp<NIN, W, D, 1, false, false, HA, OA> or MmProd<RAW>.  The quadrature state of n_state = 3 enters no residual and
@@ -128,10 +136,38 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
     if (active) refine_store(r, i, st);
 }
 
+// ... with a replicate dimension (RefineReps): the kernel's own copy of the argument block gets its observations pointed at the
+// replicate's, the sweep and the rule are the calls above
 template <class Net>
-static hipError_t launch_cpep_fused(int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) void cpep_refine_reps_kernel(CpepArgs a, RefineCfg k, RefineArrays r,
+                                                                                                          RefineReps p) {
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x;
+    const int64_t gid = ((int64_t)blockIdx.x + p.blk_first) * kBlock + lane;
+    const bool active = gid < a.N;
+    const int64_t i = active ? gid : a.N - 1;
+    a.obs = p.slab + (int64_t)blockIdx.y * p.slab_stride;
+
+    const CpepTanConst kc = cpep_tan_load<Net>(a, i);
+    RefineLane st;
+    refine_start(st, k, r.x0[i], active);
+#pragma unroll 1
+    while (__ballot(st.status == kRefineRunning) != 0ull) {
+        const TanSums e = cpep_tan_sweep<Net, 2>(a, kc, i, lane, st.xt, smem, TanNoStore());
+        refine_update(st, k, e.sse, e.score + e.chk, e.info + e.chk);
+    }
+    if (active) refine_store_rep(r, (int64_t)blockIdx.y * p.rep_stride + i, st);
+}
+
+template <class Net>
+static hipError_t launch_cpep_fused(int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps) {
     const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
     const size_t lds = sizeof(double) * (size_t)10 * kBlock;
+    if (reps != nullptr) {
+        hipLaunchKernelGGL((cpep_refine_reps_kernel<Net>), dim3((unsigned)reps->blk_count, (unsigned)reps->n_reps), dim3(kBlock), lds, s, a,
+                           k, r, *reps);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((cpep_refine_kernel<Net>), dim3((unsigned)nblocks), dim3(kBlock), lds, s, a, k, r);
     return hipGetLastError();
 }
@@ -169,34 +205,34 @@ hipError_t launch_refine_step(int phase, const RefineCfg& k, const RefineArrays&
     return hipGetLastError();
 }
 
-hipError_t launch_cpep_refine(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
+hipError_t launch_cpep_refine(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps) {
     if (net.generic() || a.obs == nullptr || a.T < 1 || a.S < 1 || (n_state != 2 && n_state != 3)) return hipErrorInvalidValue;
     if (net.symbolic())
-        return a.cond_raw ? launch_cpep_fused<MmProd<true>>(n_state, a, k, r, s) : launch_cpep_fused<MmProd<false>>(n_state, a, k, r, s);
-    if (net.general()) return launch_cpep_refine_part1(net, n_state, a, k, r, s);
+        return a.cond_raw ? launch_cpep_fused<MmProd<true>>(n_state, a, k, r, s, reps) : launch_cpep_fused<MmProd<false>>(n_state, a, k, r, s, reps);
+    if (net.general()) return launch_cpep_refine_part1(net, n_state, a, k, r, s, reps);
     hipError_t e = visit_cpep_shapes_0(net, hipErrorNotSupported, [&](auto sh) {
-        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s);
+        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s, reps);
     });
-    if (e == hipErrorNotSupported) e = launch_cpep_refine_part1(net, n_state, a, k, r, s);
-    return e != hipErrorNotSupported ? e : launch_cpep_refine_part2(net, n_state, a, k, r, s);
+    if (e == hipErrorNotSupported) e = launch_cpep_refine_part1(net, n_state, a, k, r, s, reps);
+    return e != hipErrorNotSupported ? e : launch_cpep_refine_part2(net, n_state, a, k, r, s, reps);
 }
 
 #elif CUDE_REFINE_PART == 1
 // hipErrorNotSupported = not in this group
-hipError_t launch_cpep_refine_part1(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
+hipError_t launch_cpep_refine_part1(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps) {
     if (net.general())
         return visit_cpep_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
-            return launch_cpep_fused<CpepNetG<sh.nin, sh.width, sh.depth, act.hact, act.oact>>(n_state, a, k, r, s);
+            return launch_cpep_fused<CpepNetG<sh.nin, sh.width, sh.depth, act.hact, act.oact>>(n_state, a, k, r, s, reps);
         });
     return visit_cpep_shapes_1(net, hipErrorNotSupported, [&](auto sh) {
-        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s);
+        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s, reps);
     });
 }
 
 #elif CUDE_REFINE_PART == 2
-hipError_t launch_cpep_refine_part2(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
+hipError_t launch_cpep_refine_part2(const NetShape& net, int n_state, const CpepArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps) {
     return visit_cpep_shapes_2(net, hipErrorInvalidValue, [&](auto sh) {
-        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s);
+        return launch_cpep_fused<Mlp<sh.nin, sh.width, sh.depth, 1>>(n_state, a, k, r, s, reps);
     });
 }
 
@@ -222,22 +258,50 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
     if (active) refine_store(r, i, rs);
 }
 
+// ... with a replicate dimension, as cpep_refine_reps_kernel
+template <int W, int D, int HA, int OA>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) void supp_refine_reps_kernel(SuppArgs a, RefineCfg k, RefineArrays r,
+                                                                                                          RefineReps p) {
+    using Net = Mlp<4, W, D, 3, false, false, HA, OA>;
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x;
+    const int64_t gid = ((int64_t)blockIdx.x + p.blk_first) * kBlock + lane;
+    const bool active = gid < a.N;
+    const int64_t i = active ? gid : a.N - 1;
+    a.data = p.slab + (int64_t)blockIdx.y * p.slab_stride;
+
+    const SuppTanConst kc = supp_tan_load<Net>(a, i);
+    RefineLane rs;
+    refine_start(rs, k, r.x0[i], active);
+#pragma unroll 1
+    while (__ballot(rs.status == kRefineRunning) != 0ull) {
+        const TanSums e = supp_tan_sweep<Net>(a, kc, i, lane, rs.xt, smem, TanNoStore());
+        refine_update(rs, k, e.sse, e.score, e.info);
+    }
+    if (active) refine_store_rep(r, (int64_t)blockIdx.y * p.rep_stride + i, rs);
+}
+
 template <int W, int D, int HA = kActHiddenTanh, int OA = kActOutSoftplus>
-static hipError_t launch_supp_fused(const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
+static hipError_t launch_supp_fused(const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps) {
     const int64_t nblocks = (a.N + kBlock - 1) / kBlock;
+    if (reps != nullptr) {
+        hipLaunchKernelGGL((supp_refine_reps_kernel<W, D, HA, OA>), dim3((unsigned)reps->blk_count, (unsigned)reps->n_reps), dim3(kBlock),
+                           sizeof(double) * (size_t)(7 * 4) * kBlock, s, a, k, r, *reps);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((supp_refine_kernel<W, D, HA, OA>), dim3((unsigned)nblocks), dim3(kBlock),
                        sizeof(double) * (size_t)(7 * 4) * kBlock, s, a, k, r);
     return hipGetLastError();
 }
 
-hipError_t launch_supp_refine(const NetShape& net, const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s) {
+hipError_t launch_supp_refine(const NetShape& net, const SuppArgs& a, const RefineCfg& k, const RefineArrays& r, hipStream_t s, const RefineReps* reps) {
     if (net.nin != 4 || net.generic() || a.T < 1 || a.T_data > 0 || a.rho == nullptr || a.obs_rho == nullptr || a.S < 1)
         return hipErrorInvalidValue;
     if (net.general())
         return visit_supp_general(net, hipErrorInvalidValue, [&](auto sh, auto act) {
-            return launch_supp_fused<sh.width, sh.depth, act.hact, act.oact>(a, k, r, s);
+            return launch_supp_fused<sh.width, sh.depth, act.hact, act.oact>(a, k, r, s, reps);
         });
-    return visit_supp_shapes(net, hipErrorInvalidValue, [&](auto sh) { return launch_supp_fused<sh.width, sh.depth>(a, k, r, s); });
+    return visit_supp_shapes(net, hipErrorInvalidValue, [&](auto sh) { return launch_supp_fused<sh.width, sh.depth>(a, k, r, s, reps); });
 }
 #endif
 

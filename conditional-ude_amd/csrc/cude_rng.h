@@ -49,6 +49,23 @@ __device__ __forceinline__ double rng_uniform(const RngKey& key, int64_t i) {
     return u01(c[0], c[1]);
 }
 
+// Block kind 2, the parametric bootstrap's noise (cude_bootstrap_conditional rule 3, cude_bootstrap.hip): counter = (global
+// subject index [64 bits], replicate [low 32 bits], kRngKindBootstrap | replicate [bits 32..46] << 16 | residual row), one
+// standard normal per block by the Box-Muller form of rng_normal (replicates below kRngMaxReplicate = 2^47,
+// cude_kernels.h).  The top bit of the last word keeps these blocks apart from the Metropolis blocks of every step below
+// 2^62.  A draw depends on (seed, subject, replicate, row) alone.
+constexpr uint32_t kRngKindBootstrap = 0x80000000u;
+__device__ __forceinline__ double rng_bootstrap_normal(uint64_t seed, int64_t subject_global, int64_t rep, int row) {
+    uint32_t c[4];
+    c[0] = (uint32_t)(uint64_t)subject_global;
+    c[1] = (uint32_t)((uint64_t)subject_global >> 32);
+    c[2] = (uint32_t)(uint64_t)rep;
+    c[3] = kRngKindBootstrap | ((uint32_t)((uint64_t)rep >> 32) << 16) | (uint32_t)row;
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u1 = u01(c[0], c[1]), u2 = u01(c[2], c[3]);
+    return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+}
+
 // proposal of subject i: state + proposal_std * standard normal (host row z, or the device stream)
 __device__ __forceinline__ double mh_proposal(const double* __restrict__ p, const double* __restrict__ z, const RngKey& key,
                                               double proposal_std, int64_t i) {

@@ -1036,6 +1036,49 @@ def wald_confidence_intervals(betas, neural_network_parameters, models, timepoin
     return _wald(betas, se, level)
 
 
+def _bootstrap(eng, center, sigma, n_rows, n_reps, level, seed, noise, lower, upper, return_replicates):
+    """The percentile interval, spread and bias of every subject's refitted conditional parameter, from the order statistics
+    and summaries cude_bootstrap_conditional leaves (the context's shared parameters are set; `center` (N,) its centre)."""
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must lie inside (0, 1)")
+    B = int(n_reps)
+    if sigma is None:                                      # the per-subject maximum-likelihood value SSE_i / n_i
+        eng.set_params(None, center)
+        sigma = np.sqrt(eng.forward(want_sse=True)["sse"] / n_rows)
+        sigma = np.where(np.isfinite(sigma), sigma, 0.0)   # (a failed subject fails through its centre's solve)
+    if noise is None and seed is not None:
+        eng.set_rng(seed)
+    ranks, lo, hi, g = quantile_ranks([0.5 - level / 2, 0.5 + level / 2], B)
+    r = eng.bootstrap_conditional(sigma, B, center, ranks=ranks, noise=noise, lower=lower, upper=upper,
+                                  want_replicates=return_replicates)
+    bounds = quantile_lerp(r["order"][lo], r["order"][hi], g[:, None])        # (2, N)
+    bounds[:, r["n_used"] < B] = np.nan                    # fewer values than asked for: not the requested quantiles
+    out = SimpleNamespace(lower=bounds[0], upper=bounds[1], se=r["sd"], bias=r["mean"] - center, mean=r["mean"],
+                          n_used=r["n_used"], sigma=np.broadcast_to(np.asarray(sigma, dtype=np.float64), center.shape).copy(),
+                          level=float(level))
+    if return_replicates:
+        out.replicates, out.status = r["replicates"], r["status"]
+    return out
+
+
+def bootstrap_conditional(betas, nn, models, timepoints, cpeptide_data, *, sigma=None, n_reps=200, level=0.95, seed=None,
+                          noise=None, lower=-4.0, upper=1.0, n_steps=None, return_replicates=False):
+    """Parametric bootstrap of every subject's conditional parameter on the device (cude_bootstrap_conditional) -- the
+    finite-sample counterpart of conditional_standard_errors / wald_confidence_intervals, by the reference's own way of
+    validating an estimate (simulate noisy data from the model, fit again: suppression/src/suppression_model.jl:39-63,
+    :179-222): n_reps times per subject, c-peptide observations are drawn around the model's prediction at betas with
+    standard deviation sigma_i (None: sqrt(SSE_i(betas_i) / n_i), conditional_standard_errors' convention) and the
+    parameter is refitted from betas_i inside [lower, upper] by estimate_conditional's method = "newton" iteration.
+    noise (n_reps, T, N) standard normals (the t_0 row is ignored), or None: the device's counter-based stream, seeded by
+    `seed` when given.  Returns a namespace: lower, upper (N,) -- the type-7 percentile interval at `level` --, se (the
+    replicates' standard deviation), bias (their mean - betas), mean, n_used (replicates whose fit did not fail; the
+    interval is NaN where that is < n_reps), sigma [, replicates (n_reps, N), status (n_reps, N)]."""
+    pop = _population(models, timepoints, cpeptide_data, n_steps)
+    center = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).reshape(-1)[:pop.N])
+    pop.engine.set_params(nn, None)
+    return _bootstrap(pop.engine, center, sigma, len(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
+
+
 # ----------------------------------------------------------------------------- suppression model
 class _SuppPop:
     def __init__(self, data, timepoints, net, lam, n_steps, device):
@@ -1151,6 +1194,19 @@ def suppression_profile_intervals(p, args, lower_bound, upper_bound, sigma, *, s
     pop.engine.set_params(p.neural, None)
     return _profile_intervals(pop.engine, np.asarray(p.theta, dtype=np.float64).reshape(-1),
                               np.linspace(lower_bound, upper_bound, steps), sigma, target, rounds, sections, return_details)
+
+
+def suppression_bootstrap(p, args, *, sigma=None, n_reps=200, level=0.95, seed=None, noise=None, lower=-8.0, upper=5.0,
+                          n_steps=None, return_replicates=False):
+    """bootstrap_conditional for the suppression model: args = (prob, individual_data, timepoints, lambda) as
+    suppression_loss, centres p.theta, network p.neural, the box validate_suppression_model's.  Replicate data: all three
+    states around the model's prediction with standard deviation sigma_i times the state's loss scale (sigma = None:
+    sqrt(SSE_i / (3 T)) of the weighted SSE); noise (n_reps, 3 T, N) in (3, T, N) order."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, None)
+    center = np.ascontiguousarray(np.asarray(p.theta, dtype=np.float64).reshape(-1))
+    return _bootstrap(pop.engine, center, sigma, 3 * len(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
 
 
 def suppression_loss_and_gradient(p, args, *, n_steps=None):

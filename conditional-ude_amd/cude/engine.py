@@ -588,6 +588,48 @@ class Engine:
                                                 _ptr(evals), _ptr(status)))
         return {"x": x, "objective": obj, "sse": sse, "info": info, "evals": evals, "status": status}
 
+    def _residual_rows(self):
+        return self.T if self.model != MODEL_SUPP else 3 * self.T
+
+    def bootstrap_conditional(self, sigma, n_reps, center=None, *, ranks=(), noise=None, first_rep=0, lower=-4.0, upper=3.0,
+                              max_evals=40, xtol=1e-7, max_step=0.5, penalty_weight=0.0, penalty_center=0.0,
+                              want_replicates=False):
+        """Parametric bootstrap of the per-subject fits on the device (cude_bootstrap_conditional): n_reps replicate data
+        sets per subject -- forward(want_traj=True) at `center` (N,; None: the context's conditional parameters) plus
+        sigma (N,) times the state's scale times standard normals -- each refitted by refine_conditional's rule from the
+        centre.  noise (n_reps, rows, N), rows = T (c-peptide models) or 3 T in (3, T, N) order (suppression); None: the
+        device stream of set_rng at replicates first_rep ... (bootstrap_noise returns those draws).  Returns dict(order
+        (len(ranks), N) -- None without ranks --, mean, sd (N,), n_used (N,) int32 [, replicates (n_reps, N), status
+        (n_reps, N) int32 = REFINE_*]): summaries over a subject's non-FAILED replicates, NaN where there are too few."""
+        B = int(n_reps)
+        sg = np.ascontiguousarray(np.broadcast_to(_f64(sigma), (self.N,)))
+        cen = None if center is None else np.ascontiguousarray(np.broadcast_to(_f64(center), (self.N,)))
+        nz = None
+        if noise is not None:
+            nz = _f64(noise)
+            if nz.shape != (B, self._residual_rows(), self.N):
+                raise ValueError(f"expected noise ({B}, {self._residual_rows()}, {self.N})")
+        rk = np.ascontiguousarray(np.asarray(ranks, dtype=np.int32).reshape(-1))
+        order = np.empty((rk.size, self.N)) if rk.size else None
+        mean, sd, used = np.empty(self.N), np.empty(self.N), np.empty(self.N, dtype=np.int32)
+        reps = np.empty((B, self.N)) if want_replicates else None
+        status = np.empty((B, self.N), dtype=np.int32) if want_replicates else None
+        check(self._lib.cude_bootstrap_conditional(
+            self._h, _ptr(cen), _ptr(sg), int(first_rep), B, _ptr(nz), float(lower), float(upper), int(max_evals),
+            float(xtol), float(max_step), float(penalty_weight), float(penalty_center), rk.size,
+            _ptr(rk) if rk.size else None, _ptr(order), _ptr(mean), _ptr(sd), _ptr(used), _ptr(reps), _ptr(status)))
+        out = {"order": order, "mean": mean, "sd": sd, "n_used": used}
+        if want_replicates:
+            out["replicates"], out["status"] = reps, status
+        return out
+
+    def bootstrap_noise(self, first_rep, n_reps):
+        """The standard normals bootstrap_conditional(noise=None, first_rep=first_rep) draws: (n_reps, rows, N), +0.0 in the
+        rows of t_0."""
+        z = np.empty((int(n_reps), self._residual_rows(), self.N))
+        check(self._lib.cude_bootstrap_noise(self._h, int(first_rep), int(n_reps), _ptr(z)))
+        return z
+
     def mh_chain(self, normals, uniforms, sigma, prior_mean, prior_sd, proposal_std, temperature=1.0, gamma=1.0,
                  n_mc=None):
         """mh_estep that also returns every state of the chain: (accepted (N,), samples (n_mc, N)).  normals =

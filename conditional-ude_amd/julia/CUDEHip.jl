@@ -30,7 +30,7 @@ export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEMod
        profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
-       curvatures, suppression_curvatures, map_curvature,
+       curvatures, suppression_curvatures, map_curvature, bootstrap_conditional, suppression_bootstrap,
        marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores,
        network_information, n_outputs, lm_candidates, train_lm!
 
@@ -237,6 +237,42 @@ function refine_conditional(c::Ctx, x0, lower, upper; max_evals = 40, xtol = 1e-
         c.h, start === nothing ? C_NULL : pointer(start), lower, upper, max_evals, xtol, max_step, penalty_weight,
         penalty_center, x, obj, sse, info, evals, status))
     x, obj, sse, info, evals, status
+end
+
+# parametric bootstrap of those fits on the device (cude_bootstrap_conditional): n_reps replicate data sets per subject --
+# forward(c; want_traj = true) at `center` (nothing: the context's conditional parameters) plus sigma[i] times the state's
+# scale times standard normals -- each refitted by refine_conditional's rule from the centre.  rows = T (c-peptide models)
+# or 3T (suppression: row = state-major, time inside, the device's [3][T][N] order); noise N×rows×n_reps, or nothing:
+# the device stream of set_rng! at replicates first_rep ... (bootstrap_noise returns those draws).  ranks 0-based, strictly
+# increasing.  Returns (order N×n_ranks, mean, sd, n_used, replicates N×n_reps, status N×n_reps) over a subject's non-FAILED
+# replicates; replicates and status are nothing unless want_replicates
+function bootstrap_conditional(c::Ctx, sigma, n_reps::Integer, rows::Integer; center = nothing, ranks = Int32[],
+                               noise = nothing, first_rep = 0, lower = -4.0, upper = 3.0, max_evals = 40, xtol = 1e-7,
+                               max_step = 0.5, penalty_weight = 0.0, penalty_center = 0.0, want_replicates = false)
+    sg = sigma isa Real ? fill(Float64(sigma), c.N) : Vector{Float64}(vec(sigma))
+    cen = center === nothing ? nothing : Vector{Float64}(vec(center))
+    nz = noise === nothing ? nothing : Array{Float64,3}(noise)
+    nz === nothing || size(nz) == (c.N, rows, n_reps) || error("noise must be N×rows×n_reps")
+    rk = Vector{Int32}(ranks); nr = length(rk)
+    order = Matrix{Float64}(undef, c.N, nr)
+    mean = Vector{Float64}(undef, c.N); sd = similar(mean); n_used = Vector{Int32}(undef, c.N)
+    reps = want_replicates ? Matrix{Float64}(undef, c.N, n_reps) : nothing
+    status = want_replicates ? Matrix{Int32}(undef, c.N, n_reps) : nothing
+    GC.@preserve sg cen nz rk order mean sd n_used reps status check(ccall((:cude_bootstrap_conditional, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Float64, Float64, Int32, Float64, Float64, Float64,
+         Float64, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+        c.h, cen === nothing ? C_NULL : pointer(cen), sg, Int64(first_rep), Int32(n_reps),
+        nz === nothing ? C_NULL : pointer(nz), lower, upper, max_evals, xtol, max_step, penalty_weight, penalty_center, nr,
+        nr > 0 ? pointer(rk) : C_NULL, nr > 0 ? pointer(order) : C_NULL, mean, sd, n_used,
+        reps === nothing ? C_NULL : pointer(reps), status === nothing ? C_NULL : pointer(status)))
+    order, mean, sd, n_used, reps, status
+end
+# the standard normals bootstrap_conditional(...; noise = nothing, first_rep) draws: N×rows×n_reps, +0.0 in the rows of t₀
+function bootstrap_noise(c::Ctx, first_rep::Integer, n_reps::Integer, rows::Integer)
+    z = Array{Float64,3}(undef, c.N, rows, n_reps)
+    GC.@preserve z check(ccall((:cude_bootstrap_noise, LIB), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}),
+        c.h, Int64(first_rep), Int32(n_reps), z))
+    z
 end
 
 # the two ways of solving the per-subject problems behind every frozen-network estimate (keyword `method`): `search` =
@@ -1105,6 +1141,44 @@ function wald_confidence_intervals(betas, neural_network_parameters, models, tim
     [(betas[i] - z * se[i], betas[i] + z * se[i]) for i in eachindex(se)]
 end
 
+# the order statistics the type-7 quantiles (Julia's `quantile`) of K values need: (ranks 0-based, lo, hi = every level's
+# 1-based positions in `ranks`, g = its weight); and the value x_lo + g (x_hi - x_lo), anchored at the nearer neighbour
+function quantile_ranks(levels, K::Integer)
+    h = (K - 1) .* collect(Float64, levels)
+    lo = floor.(Int, h)
+    hi = min.(lo .+ 1, K - 1)
+    ranks = sort(unique(vcat(lo, hi)))
+    Vector{Int32}(ranks), [searchsortedfirst(ranks, v) for v in lo], [searchsortedfirst(ranks, v) for v in hi], h .- lo
+end
+quantile_lerp(x_lo, x_hi, g) = g >= 0.5 ? x_hi - (x_hi - x_lo) * (1 - g) : x_lo + (x_hi - x_lo) * g
+# percentile interval, spread and bias of every subject's refitted conditional parameter from what bootstrap_conditional
+# leaves on the context `c` (shared parameters set); sigma = nothing: √(SSEᵢ / rows) at the centre
+function bootstrap_summary(c::Ctx, center, sigma, rows, n_reps, level, seed, noise, lower, upper, return_replicates)
+    0 < level < 1 || error("level must lie inside (0, 1)")
+    cen = Vector{Float64}(vec(center))
+    if sigma === nothing
+        set_params!(c, nothing, cen)
+        _, sse, _ = forward(c; want_sse = true)
+        sigma = [isfinite(v) ? sqrt(v / rows) : 0.0 for v in sse]
+    end
+    noise === nothing && seed !== nothing && set_rng!(c, seed)
+    ranks, lo, hi, g = quantile_ranks((0.5 - level / 2, 0.5 + level / 2), n_reps)
+    order, mean, sd, n_used, reps, status = bootstrap_conditional(c, sigma, n_reps, rows; center = cen, ranks = ranks,
+        noise = noise, lower = lower, upper = upper, want_replicates = return_replicates)
+    bound(k) = [n_used[i] < n_reps ? NaN : quantile_lerp(order[i, lo[k]], order[i, hi[k]], g[k]) for i in 1:c.N]
+    (lower = bound(1), upper = bound(2), se = sd, bias = mean .- cen, mean = mean, n_used = n_used, sigma = sigma,
+     level = level, replicates = reps, status = status)
+end
+# parametric bootstrap of every subject's conditional parameter (cude_bootstrap_conditional): the finite-sample counterpart of
+# conditional_standard_errors / wald_confidence_intervals.  noise N×T×n_reps standard normals, or nothing: the device stream
+function bootstrap_conditional(betas, neural_network_parameters, models, timepoints, cpeptide_data; sigma = nothing,
+                               n_reps = 200, level = 0.95, seed = nothing, noise = nothing, lower = -4.0, upper = 1.0,
+                               n_steps = nothing, return_replicates = false)
+    c = population(models, timepoints, cpeptide_data; n_steps = n_steps)
+    set_params!(c, neural_network_parameters, nothing)
+    bootstrap_summary(c, betas, sigma, length(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
+end
+
 # ----------------------------------------------------------------------------------------------- suppression model
 struct SuppressionProblem          # stands in for ODEProblem(ude_lsup!, u0, tspan) with the network closed over
     network::Chain
@@ -1140,6 +1214,14 @@ function suppression_curvatures(p, (prob, individual_data, timepoints, λ); n_st
     c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
     set_params!(c, p.neural, p.theta)
     curvature(c)
+end
+# bootstrap_conditional for the suppression model: centres p.theta, network p.neural; noise N×3T×n_reps
+function suppression_bootstrap(p, (prob, individual_data, timepoints, λ); sigma = nothing, n_reps = 200, level = 0.95,
+                               seed = nothing, noise = nothing, lower = -8.0, upper = 5.0, n_steps = nothing,
+                               return_replicates = false)
+    c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
+    set_params!(c, p.neural, nothing)
+    bootstrap_summary(c, p.theta, sigma, 3 * length(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
 end
 function suppression_loss_and_gradient!(G, p, (prob, individual_data, timepoints, λ))
     c = supp_population(prob, individual_data, timepoints, λ)

@@ -356,6 +356,54 @@ int32_t cude_refine_conditional(cude_ctx* ctx, const double* x0, double lower, d
                                 double* cond_out, double* objective_out, double* sse_out, double* info_out,
                                 int32_t* evals_out, int32_t* status_out);
 
+/* Parametric bootstrap of those per-subject fits, on the device: n_reps times per subject, noisy observations are simulated
+ * from the fitted model and the conditional parameter is fitted to them again -- the reference's own way of validating an
+ * estimate (the noisy data of suppression/src/suppression_model.jl:39-63, refitted as :179-222), here with the replicate as a
+ * launch dimension instead of a host loop of uploads and cude_refine_conditional calls.  The host receives per-subject
+ * summaries (and the replicate estimates if it asks), never a replicate's data.
+ *   1. Centre and prediction: center [N], NULL = the context's conditional parameters.  yhat = the trajectory cude_forward
+ *      returns at `center` with the context's shared parameters (the same launch; adaptive mode: its accepted steps).
+ *   2. Replicate data: y*[b, r, i] = yhat[r, i] + (sigma[i] s_r) eps[b, r, i] over the residual rows r of the population's own
+ *      layout, every operation rounded on its own (no fma).  C-peptide models: the T rows of state 1, s = 1.  Suppression
+ *      model: 3 T rows in [3][T][N] order, s = the state's cude_get_scale value; the loss weights stay the population's.
+ *      The row(s) of t_0 are the population's own data, never drawn: they are the initial state and their residual is zero.
+ *   3. Noise: eps = noise[(b rows + r) N + i] ([n_reps][rows][N]; entries of t_0 rows are ignored), or with noise == NULL
+ *      the context's Philox stream (cude_set_rng): key = seed, counter = (global subject, first_rep + b, row) in a block kind
+ *      of its own, Box-Muller as the Metropolis draws.  A draw depends on nothing else: identical under any chunking and any
+ *      sharding (cude_set_rng's subject_offset).  The context keeps no position: first_rep is the caller's (0 <= first_rep,
+ *      first_rep + n_reps <= 2^47).  cude_bootstrap_noise returns exactly the draws such a call uses ([n_reps][rows][N], +0.0
+ *      in the t_0 rows).
+ *   4. Fits: replicate b of subject i runs cude_refine_conditional's rule (above, steps 1-6, the same device statement) from
+ *      x0 = center_i on the replicate's data, with the same box, max_evals, xtol, max_step and penalty.  reps_out and
+ *      status_out ([n_reps][N], optional): the points reached and their CUDE_REFINE_* status.  No forward launch follows the
+ *      iteration: objectives, SSEs and evaluation counts are not reported.
+ *   5. Summaries per subject over its non-FAILED replicates, in replicate order: n_used_out[i] = their count; mean_out[i] =
+ *      (((x_0 + x_1) + x_2) + ...) / n_used; sd_out[i] = sqrt(sum (x_b - mean)^2 / (n_used - 1)), a second pass, NaN for
+ *      n_used < 2; order_out[r N + i] ([n_ranks][N]) = the ranks[r]-th smallest (0-based) of the non-FAILED estimates -- a
+ *      selection: one of the replicate estimates, bit for bit -- and NaN where ranks[r] >= n_used.  ranks strictly increasing
+ *      inside [0, n_reps); 0 <= n_ranks <= 16, order_out exactly when n_ranks > 0; at least one output.  mean, sd and order
+ *      are NaN with n_used == 0.  The reduction runs over all replicates of a subject at once: every output is bit-identical
+ *      for every chunking.
+ *   6. CUDE_ERR_ARG for a negative or non-finite sigma entry, for the box, step, penalty and rank errors of
+ *      cude_refine_conditional / cude_predictive_bands, and for n_reps outside [1, 4096].  A non-finite center_i fails that
+ *      subject alone: all its statuses FAILED, n_used 0, its summaries NaN; cude_n_failed afterwards counts the subjects
+ *      with a FAILED replicate.
+ *   7. CUDE_ERR_UNSUPPORTED for a network on the fallback kernel (cude_set_network), CUDE_ERR_STATE under stream capture.
+ *   8. Uses the context's shared parameters, leaves its conditional parameters untouched.  Adaptive mode: cude_adaptive_steps
+ *      refuses afterwards.
+ * Fixed-step mode: the fused kernels of cude_refine_conditional with the replicate in the grid's second dimension -- ONE
+ * launch fits a chunk of replicates of all subjects; replicates per launch by ~256 MB of replicate data (option
+ * "bootstrap_chunk"), subjects per pass in whole workgroups of 64 by ~1 GB of replicate results (option
+ * "bootstrap_subjects"); one stream, no graph.  Adaptive mode and option "refine_fused" = 0: the stepped form, ONE REPLICATE AT
+ * A TIME (max_evals tangent launches over the whole population per replicate, all queued) -- slow, n_reps times the cost of
+ * a stepped cude_refine_conditional; meant for checking, not for production runs. */
+int32_t cude_bootstrap_conditional(cude_ctx* ctx, const double* center, const double* sigma, int64_t first_rep,
+                                   int32_t n_reps, const double* noise, double lower, double upper, int32_t max_evals,
+                                   double xtol, double max_step, double penalty_weight, double penalty_center,
+                                   int32_t n_ranks, const int32_t* ranks, double* order_out, double* mean_out,
+                                   double* sd_out, int32_t* n_used_out, double* reps_out, int32_t* status_out);
+int32_t cude_bootstrap_noise(cude_ctx* ctx, int64_t first_rep, int32_t n_reps, double* noise_out);
+
 /* Per-subject profile-likelihood intervals with the whole profile kept on the device -- the loop around
  * `find_confidence_intervals(loss_values, loss_minimum, parameter_values; target)` (src/likelihood-profiles.jl:34-59, run
  * for every subject over 1000-10000 profile points at c-peptide/02-conditional.jl:186-188).  The host receives a handful
@@ -850,10 +898,12 @@ int32_t cude_xchg_info(cude_ctx* ctx, int32_t* n_ranks, int32_t* rank, int32_t* 
  * kernel, the default; 0 = one tangent launch per evaluation), "profile_chunk" (cude_profile_conditional / cude_profile_intervals:
  * grid points per launch, 0 = ~512 MB of scratch; tests force several launches with it), "predictive_subjects" /
  * "predictive_times" (cude_predictive_bands: subjects per solve launch, rounded up to 64, and output times per launch; 0 =
- * by the ~1 GB budget of sample trajectories; tests force several launches in either dimension with them).  Values are decimal integers as text unless noted.  Every option is also read once
+ * by the ~1 GB budget of sample trajectories; tests force several launches in either dimension with them), "bootstrap_chunk" /
+ * "bootstrap_subjects" (cude_bootstrap_conditional: replicates per launch and subjects per pass, rounded up to 64; 0 = by the
+ * ~256 MB / ~1 GB budgets; tests force either split with them).  Values are decimal integers as text unless noted.  Every option is also read once
  * at cude_create from its environment variable (CUDE_CPEP_PATH, CUDE_CPEP_KEEP, CUDE_SUPP_STORE, CUDE_SUPP_CKPT,
  * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED, CUDE_PROFILE_CHUNK,
- * CUDE_PREDICTIVE_SUBJECTS, CUDE_PREDICTIVE_TIMES).
+ * CUDE_PREDICTIVE_SUBJECTS, CUDE_PREDICTIVE_TIMES, CUDE_BOOTSTRAP_CHUNK, CUDE_BOOTSTRAP_SUBJECTS).
  * Options that shape the launch path take effect at the next cude_set_population_*.  No reference line: these are
  * properties of this implementation. */
 int32_t cude_set_option(cude_ctx* ctx, const char* name, const char* value);
