@@ -245,7 +245,8 @@ end
 # or 3T (suppression: row = state-major, time inside, the device's [3][T][N] order); noise N×rows×n_reps, or nothing:
 # the device stream of set_rng! at replicates first_rep ... (bootstrap_noise returns those draws).  ranks 0-based, strictly
 # increasing.  Returns (order N×n_ranks, mean, sd, n_used, replicates N×n_reps, status N×n_reps) over a subject's non-FAILED
-# replicates; replicates and status are nothing unless want_replicates
+# replicates; replicates and status are nothing unless want_replicates.  noise is not screened: a non-finite entry outside
+# the t_0 rows fails its replicate of its subject alone (status FAILED, left out of that subject's summaries)
 function bootstrap_conditional(c::Ctx, sigma, n_reps::Integer, rows::Integer; center = nothing, ranks = Int32[],
                                noise = nothing, first_rep = 0, lower = -4.0, upper = 3.0, max_evals = 40, xtol = 1e-7,
                                max_step = 0.5, penalty_weight = 0.0, penalty_center = 0.0, want_replicates = false)

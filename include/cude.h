@@ -387,7 +387,8 @@ int32_t cude_refine_conditional(cude_ctx* ctx, const double* x0, double lower, d
  *   6. CUDE_ERR_ARG for a negative or non-finite sigma entry, for the box, step, penalty and rank errors of
  *      cude_refine_conditional / cude_predictive_bands, and for n_reps outside [1, 4096].  A non-finite center_i fails that
  *      subject alone: all its statuses FAILED, n_used 0, its summaries NaN; cude_n_failed afterwards counts the subjects
- *      with a FAILED replicate.
+ *      with a FAILED replicate.  The caller's noise is not screened: a non-finite entry outside the t_0 rows fails its
+ *      replicate of its subject alone (that fit's first objective is non-finite), which rule 5 then leaves out.
  *   7. CUDE_ERR_UNSUPPORTED for a network on the fallback kernel (cude_set_network), CUDE_ERR_STATE under stream capture.
  *   8. Uses the context's shared parameters, leaves its conditional parameters untouched.  Adaptive mode: cude_adaptive_steps
  *      refuses afterwards.

@@ -1,6 +1,8 @@
 """cude_bootstrap_conditional without a GPU: the admissibility of the cases tests/test_gpu_bootstrap.py holds the device to,
 the numpy restatement's summaries (tests/bootstrap_ref.py) against numpy's own statistics, the mirror's percentile interval
-against numpy.quantile, the draws' counter layout, the ABI surface and the cross-compilation of the new translation unit.
+against numpy.quantile, the draws' counter layout, the ABI surface and the cross-compilation of the new translation unit;
+and, on the restatement alone, the conditions tests/test_gpu_bootstrap_shapes.py and tests/test_gpu_set_reductions.py put on
+their cases (the replicates move their subjects; non-finite noise fails exactly its replicate).
 
 Admissibility.  A (replicate, subject) pair is UNSTABLE when the restatement's status or `evals` change under f_info,
 f_score = 1 +- 1e-9, together and in opposite directions -- the error the tangent kernels are allowed, the study of
@@ -59,6 +61,76 @@ def test_sigma_zero_gives_the_prediction_itself():
     assert y.shape == (6, 3, 5, 4)
     assert np.array_equal(y[:, :, 1:], np.broadcast_to(yhat[:, 1:], (6, 3, 4, 4)))
     assert np.array_equal(y[:, :, 0], np.broadcast_to(pop[:, 0], (6, 3, 4)))
+
+
+# ----------------------------------------------------------------------------- the per-shape and partial-failure cases
+SHAPE_CASES = [("cpep", 0, ()), ("cpep", 1, ()), ("cpep", 8, ()), ("supp", 0, ()), ("supp", 10, ()), ("cpep", 2, ("relu", "softplus")),
+               ("supp", 0, ("sigmoid", "identity")), ("supp", 5, ("sigmoid", "softplus"))]
+
+
+@pytest.mark.parametrize("model,k,acts", SHAPE_CASES, ids=[f"{m}-{k}-{'-'.join(a)}" for m, k, a in SHAPE_CASES])
+def test_shape_cases_move_their_subjects(model, k, acts):
+    """Check 2 of tests/test_gpu_bootstrap_shapes.py (assert_case_can_fail there) on the restatement, with that file's
+    inputs -- tangent_case, centre = its conditional parameters, sigma = sqrt(SSE / rows) there, default_rng(17): at least
+    three quarters of the subjects that the box does not pin get three pairwise different replicate estimates, none equal
+    to the fit of the population's own data, and every replicate has estimates that no other data give -- so a kernel that
+    read the population, or one replicate's slab for every replicate, cannot pass.  The population's data ride along as
+    a fourth replicate of the stacked population.  Cases: the first shape of a group of either model, two small ones, and
+    the four whose fits run into the box most (the last is that file's one PINNED_CASES entry)."""
+    import adaptive_cases as ac
+    import bootstrap_ref as br
+    import cude_oracle as o
+    import refine_ref as rr
+    import test_gpu_bootstrap_shapes as bs
+    c, cond, box = ac.tangent_case(model, k)
+    tag = f"{model} {c['arch']} {'-'.join(acts)}".strip()
+    c = dict(c, arch=tuple(c["arch"]) + tuple(acts))
+    center, N, T = c[cond], c[cond].size, len(c["tp"])
+    if model == "supp":
+        rows, pop, scale = 3 * T, np.asarray(c["data"], dtype=np.float64), o.supp_scale(c["data"])
+        yhat = br.supp_yhat(c, center)
+        sse = br.supp_evaluator(c, pop, scale)(center)[2]
+    else:
+        rows, pop, scale = T, np.asarray(c["obs"], dtype=np.float64).T[None], np.ones(1)
+        yhat = br.cpep_yhat(c, center)
+        sse = rr.cpep_evaluator(c)(center)[2]
+    noise = np.random.default_rng(bs.NOISE_SEED).standard_normal((bs.B, rows, N))
+    ystar = np.concatenate([br.replicate_data(yhat, np.sqrt(sse / rows), scale, noise, pop), pop[None]])
+    ev = br.supp_evaluator(c, br.supp_stacked_data(ystar), scale) if model == "supp" else rr.cpep_evaluator(br.cpep_stacked(c, ystar))
+    fit = br.refit(ev, center, bs.B + 1, *box, xtol=1e-7, max_step=0.5)
+    bs.assert_case_can_fail(tag, fit["x"], fit["status"])
+
+
+def test_nonfinite_noise_fails_its_replicate_alone_in_the_restatement():
+    """The K = 5 case of tests/test_gpu_set_reductions.py::test_partly_failed_subjects on the restatement: by rule 1 of
+    cude_refine_conditional a non-finite noise entry behind t_0 makes that replicate's first objective non-finite, so
+    exactly the planned (replicate, subject) pairs are FAILED and every other pair is what it was; an entry of a t_0 row
+    changes nothing (rule 3)."""
+    import bootstrap_ref as br
+    import refine_ref as rr
+    import test_gpu_set_reductions as sr
+    K, chunk = 5, 2
+    c, center, sigma, noise = sr.boot_inputs()
+    N, T = sr.N_BOOT, len(c["tp"])
+    pop, yhat = np.asarray(c["obs"], dtype=np.float64).T[None], br.cpep_yhat(c, center)
+    plan = sr.failure_plan(K, chunk)
+    want = np.zeros((K, N), dtype=bool)
+    z0 = noise[:K].copy()
+    for b, i, v in plan:
+        want[b, i] = True
+        z0[b, 0, i] = v
+    assert np.array_equal(br.replicate_data(yhat, sigma, np.ones(1), z0, pop), br.replicate_data(yhat, sigma, np.ones(1), noise[:K], pop))
+    fits = []
+    for z in (noise[:K], sr.poisoned(noise[:K], plan, T)):
+        ystar = br.replicate_data(yhat, sigma, np.ones(1), z, pop)
+        fits.append(br.refit(rr.cpep_evaluator(br.cpep_stacked(c, ystar)), center, K, -4.0, 3.0, xtol=1e-7, max_step=0.5))
+    clean, got = fits
+    assert not np.any(clean["status"] == rr.FAILED)
+    assert np.array_equal(got["status"] == rr.FAILED, want)
+    assert np.array_equal(got["x"][~want], clean["x"][~want]) and np.array_equal(got["status"][~want], clean["status"][~want])
+    s = br.summaries(got["x"], got["status"], sr.boot_ranks(K))
+    assert np.array_equal(s["n_used"], K - want.sum(axis=0)) and sorted(set(want.sum(axis=0).tolist())) == [0, 1, 2, K - 1, K]
+    assert np.array_equal(np.isnan(s["order"]), sr.boot_ranks(K)[:, None] >= s["n_used"][None, :])
 
 
 # ----------------------------------------------------------------------------- rule 5
