@@ -1,6 +1,6 @@
 // libcude_hip.so -- the entry points that batch launches: dense output and predictive bands, conditional sets, marginal
 // likelihoods, subject scores, network information, sensitivities, multi-start evaluation and screening, likelihood
-// profiles and their intervals, per-subject fits and their parametric bootstrap.  Each is its own argument checks, chunking, small kernels and copies
+// profiles and their intervals, per-subject fits and their parametric bootstrap, prediction discrepancies and npde.  Each is its own argument checks, chunking, small kernels and copies
 // around the launches of cude_launch.hip, in chunks sized by cude_select.hip's sets_per_launch.
 #include "cude_ctx.h"
 
@@ -1307,6 +1307,159 @@ int32_t cude_bootstrap_noise(cude_ctx* c, int64_t first_rep, int32_t n_reps, dou
         HIP_TRY(cude::launch_bootstrap_noise(g, d_eps.p, c->stream));
         HIP_TRY(fetch(c, noise_out + (size_t)k0 * rows * N, d_eps.p, (size_t)kn * rows * N));
         HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return CUDE_OK;
+}
+
+int32_t cude_npde(cude_ctx* c, int32_t n_sims, const double* cond_sets, double prior_mean, double prior_sd, const double* sigma,
+                  int64_t first_rep, const double* noise, int32_t state, double* pred_mean_out, double* pred_var_out,
+                  int32_t* below_out, int32_t* below_decorr_out, double* pd_out, double* npde_out, int32_t* n_used_out,
+                  int32_t* status_out, double* sims_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (c->net.generic())
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_npde: the network of this context runs on the fallback kernel "
+                                          "(cude_set_network), whose dense output takes one parameter set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_npde under stream capture");
+    if (n_sims < 2 || n_sims > cude::kPredMaxSets) return fail(CUDE_ERR_ARG, "need 2 <= n_sims <= 4096");
+    if (first_rep < 0 || first_rep > cude::kRngMaxReplicate - n_sims) return fail(CUDE_ERR_ARG, "need 0 <= first_rep, first_rep + n_sims <= 2^47");
+    const bool cpep = is_cpep(c);
+    const int NS = cpep ? c->cfg.n_state : 3;
+    if (state < 0 || state >= (cpep ? 1 : 3)) return fail(CUDE_ERR_ARG, "state out of range (c-peptide models: 0, the observed state)");
+    if (!cond_sets && (!(prior_sd > 0) || !std::isfinite(prior_sd) || !std::isfinite(prior_mean)))
+        return fail(CUDE_ERR_ARG, "need finite prior_mean and prior_sd > 0 when cond_sets is null");
+    if (!pred_mean_out && !pred_var_out && !below_out && !below_decorr_out && !pd_out && !npde_out && !n_used_out && !status_out &&
+        !sims_out)
+        return fail(CUDE_ERR_ARG, "no output requested");
+    if (!sigma) return fail(CUDE_ERR_ARG, "null sigma");
+    const int64_t N = c->N, K = n_sims, nb = c->nblocks;
+    for (int64_t i = 0; i < N; i++)
+        if (sigma[i] < 0) return fail(CUDE_ERR_ARG, "sigma must not be negative");
+    const int T = c->T, R = T - 1, P = c->P;
+    if (R < 1) return fail(CUDE_ERR_ARG, "the population has no data time after t_0");
+    // Subjects per pass: whole workgroups, as many as ~1 GB of trajectories ([K][subjects][T][NS]), simulated observations
+    // ([K][R][subjects]) and their flags allow -- all K simulations of a subject are resident when it is reduced
+    const double per_block = ((8.0 * NS * T + 8.0 * R + 1.0) * (double)K) * cude::kBlock;
+    int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)(1e9 / per_block)));
+    if (c->opt.npde_subjects > 0) blocks = std::min<int64_t>(nb, ((int64_t)c->opt.npde_subjects + cude::kBlock - 1) / cude::kBlock);
+    const int64_t sub_max = std::min<int64_t>(N, blocks * cude::kBlock);
+    DevBuf<double> d_cond, d_slab, d_y, d_part, d_sigma, d_out;
+    DevBuf<int32_t> d_int;
+    DevBuf<uint8_t> d_used;
+    OutputTables tables;
+    HIP_TRY(d_cond.resize((size_t)K * N));
+    HIP_TRY(d_sigma.resize((size_t)N));
+    HIP_TRY(d_slab.resize((size_t)K * sub_max * T * NS));
+    HIP_TRY(d_y.resize((size_t)K * R * sub_max));
+    HIP_TRY(d_used.resize((size_t)K * sub_max));
+    if (cpep || adaptive(c)) HIP_TRY(d_part.resize((size_t)K * blocks * (P + 2)));
+    HIP_TRY(d_out.resize((size_t)4 * R * N));            // pred_mean, pred_var, pd, npde: [R][N] each
+    HIP_TRY(d_int.resize((size_t)(2 * R + 2) * N + 1));   // below, below_decorr [R][N]; n_used, status [N]; failed subjects
+    cude::NpdeReduceArgs ra{};
+    ra.N = N; ra.K = (int32_t)K; ra.R = R;
+    ra.y = d_y.p; ra.used = d_used.p; ra.sigma = d_sigma.p;
+    ra.obs = cpep ? c->obs.p : c->data.p + (size_t)state * T * N;
+    ra.pred_mean = d_out.p; ra.pred_var = d_out.p + (size_t)R * N; ra.pd = d_out.p + (size_t)2 * R * N;
+    ra.npde = d_out.p + (size_t)3 * R * N;
+    ra.below = d_int.p; ra.below_decorr = d_int.p + (size_t)R * N;
+    ra.n_used = d_int.p + (size_t)2 * R * N; ra.status = ra.n_used + N; ra.n_failed = ra.status + N;
+    if (!below_decorr_out && !npde_out) { ra.below_decorr = nullptr; ra.npde = nullptr; }     // (the substitution is skipped)
+    HIP_TRY(hipMemsetAsync(ra.n_failed, 0, sizeof(int32_t), c->stream));
+    HIP_TRY(push(c, d_sigma.p, sigma, N));
+    if (cond_sets) HIP_TRY(push(c, d_cond.p, cond_sets, K * N));
+    else {
+        cude::NpdePlaceArgs pl{};
+        pl.N = N; pl.K = (int32_t)K; pl.normals_only = 0; pl.prior_mean = prior_mean; pl.prior_sd = prior_sd;
+        pl.seed = c->rng_seed; pl.subject_offset = c->rng_offset; pl.first_rep = first_rep; pl.out = d_cond.p;
+        HIP_TRY(cude::launch_npde_place(pl, c->stream));
+    }
+    if ((rc = tables.upload(c, T, c->tp.data()))) return rc;
+    DenseLaunch d;                                        // K sets at the data's own times; the caller's order of subjects
+    d.cond = d_cond.p; d.n_sets = (int32_t)K; d.partials = d_part.p; d.keep_perm = false;
+    d.traj_ss = 1; d.traj_st = 3; d.traj_sn = 3 * T;
+    d.k0 = 0; d.kn = T;
+    cude::NpdeObserveArgs oa{};
+    oa.K = (int32_t)K; oa.T = T; oa.NS = NS; oa.state = state; oa.from_noise = noise ? 1 : 0;
+    oa.scale = cpep ? 1.0 : c->scale[state];
+    oa.slab = d_slab.p; oa.sigma = d_sigma.p; oa.y = d_y.p; oa.used = d_used.p;
+    oa.seed = c->rng_seed; oa.subject_offset = c->rng_offset; oa.first_rep = first_rep;
+    const size_t pitch_host = (size_t)N * sizeof(double);
+    for (int64_t b0 = 0; b0 < nb; b0 += blocks) {
+        const int64_t bn = std::min<int64_t>(blocks, nb - b0);
+        const int64_t s0 = b0 * cude::kBlock, sn = std::min<int64_t>(N, (b0 + bn) * cude::kBlock) - s0;
+        const int64_t set_stride = (int64_t)NS * T * sn;
+        // outputs a failed adaptive solve does not reach stay NaN
+        if (adaptive(c)) HIP_TRY(hipMemsetAsync(d_slab.p, 0xff, (size_t)K * set_stride * sizeof(double), c->stream));
+        // subject i of the population writes column block (i - s0) of the slab
+        d.traj = d_slab.p - (int64_t)NS * T * s0;
+        d.set_stride = set_stride; d.blk_first = b0; d.blk_count = bn;
+        if ((rc = launch_dense(c, tables, d))) return rc;
+        // the caller's noise of these subjects goes into the table of simulated observations and is turned into them in place
+        if (noise)
+            HIP_TRY(hipMemcpy2DAsync(d_y.p, (size_t)sn * sizeof(double), noise + s0, pitch_host, (size_t)sn * sizeof(double),
+                                     (size_t)K * R, hipMemcpyHostToDevice, c->stream));
+        oa.subj0 = s0; oa.n_subj = sn;
+        HIP_TRY(cude::launch_npde_observe(oa, c->stream));
+        ra.subj0 = s0; ra.n_subj = sn;
+        HIP_TRY(cude::launch_npde_reduce(ra, c->stream));
+        if (sims_out)
+            HIP_TRY(hipMemcpy2DAsync(sims_out + s0, pitch_host, d_y.p, (size_t)sn * sizeof(double), (size_t)sn * sizeof(double),
+                                     (size_t)K * R, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));         // the slab and the tables are the next pass's too
+    }
+    int32_t failed = 0;
+    HIP_TRY(fetch(c, pred_mean_out, d_out.p, (size_t)R * N));
+    HIP_TRY(fetch(c, pred_var_out, d_out.p + (size_t)R * N, (size_t)R * N));
+    HIP_TRY(fetch(c, pd_out, d_out.p + (size_t)2 * R * N, (size_t)R * N));
+    HIP_TRY(fetch(c, npde_out, d_out.p + (size_t)3 * R * N, (size_t)R * N));
+    HIP_TRY(fetch(c, below_out, d_int.p, (size_t)R * N));
+    HIP_TRY(fetch(c, below_decorr_out, d_int.p + (size_t)R * N, (size_t)R * N));
+    HIP_TRY(fetch(c, n_used_out, d_int.p + (size_t)2 * R * N, N));
+    HIP_TRY(fetch(c, status_out, d_int.p + (size_t)(2 * R + 1) * N, N));
+    HIP_TRY(fetch(c, &failed, d_int.p + (size_t)(2 * R + 2) * N, 1));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_failed = failed;
+    return CUDE_OK;
+}
+
+int32_t cude_npde_draws(cude_ctx* c, int64_t first_rep, int32_t n_sims, double* eta_normals_out, double* noise_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (n_sims < 1 || n_sims > cude::kPredMaxSets) return fail(CUDE_ERR_ARG, "need 1 <= n_sims <= 4096");
+    if (first_rep < 0 || first_rep > cude::kRngMaxReplicate - n_sims) return fail(CUDE_ERR_ARG, "need 0 <= first_rep, first_rep + n_sims <= 2^47");
+    if (!eta_normals_out && !noise_out) return fail(CUDE_ERR_ARG, "null output");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_npde_draws under stream capture");
+    const int64_t N = c->N;
+    const int T = c->T, R = T - 1;
+    if (noise_out && R < 1) return fail(CUDE_ERR_ARG, "the population has no data time after t_0");
+    if (eta_normals_out) {
+        DevBuf<double> d_z;
+        HIP_TRY(d_z.resize((size_t)n_sims * N));
+        cude::NpdePlaceArgs pl{};
+        pl.N = N; pl.K = n_sims; pl.normals_only = 1;
+        pl.seed = c->rng_seed; pl.subject_offset = c->rng_offset; pl.first_rep = first_rep; pl.out = d_z.p;
+        HIP_TRY(cude::launch_npde_place(pl, c->stream));
+        HIP_TRY(fetch(c, eta_normals_out, d_z.p, (size_t)n_sims * N));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (noise_out) {
+        // simulations per launch: ~256 MB of draws
+        const int64_t chunk = sets_per_launch(n_sims, 65535, 256e6, 8.0 * R * (double)N);
+        DevBuf<double> d_eps;
+        HIP_TRY(d_eps.resize((size_t)chunk * R * N));
+        cude::NpdeObserveArgs oa{};
+        oa.subj0 = 0; oa.n_subj = N; oa.T = T; oa.noise_only = 1; oa.y = d_eps.p;
+        oa.seed = c->rng_seed; oa.subject_offset = c->rng_offset;
+        for (int64_t k0 = 0; k0 < n_sims; k0 += chunk) {
+            const int64_t kn = std::min<int64_t>(chunk, n_sims - k0);
+            oa.K = (int32_t)kn; oa.first_rep = first_rep + k0;
+            HIP_TRY(cude::launch_npde_observe(oa, c->stream));
+            HIP_TRY(fetch(c, noise_out + (size_t)k0 * R * N, d_eps.p, (size_t)kn * R * N));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
     }
     return CUDE_OK;
 }

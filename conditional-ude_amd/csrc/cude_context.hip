@@ -215,6 +215,7 @@ const OptionEntry kOptions[] = {
     {"predictive_times", "CUDE_PREDICTIVE_TIMES", &Options::predictive_times, false, false},
     {"bootstrap_chunk", "CUDE_BOOTSTRAP_CHUNK", &Options::bootstrap_chunk, false, false},
     {"bootstrap_subjects", "CUDE_BOOTSTRAP_SUBJECTS", &Options::bootstrap_subjects, false, false},
+    {"npde_subjects", "CUDE_NPDE_SUBJECTS", &Options::npde_subjects, false, false},
 };
 }  // namespace
 

@@ -103,6 +103,8 @@ struct Options {
                                 //   as ~256 MB of replicate observations allow)
     int bootstrap_subjects = 0; // "bootstrap_subjects" / CUDE_BOOTSTRAP_SUBJECTS: its subjects per pass, rounded up to whole workgroups of
                                 //   64 (0 = as many as ~1 GB of replicate results allow); tests force either split with them
+    int npde_subjects = 0;      // "npde_subjects" / CUDE_NPDE_SUBJECTS: subjects per pass of cude_npde, rounded up to whole workgroups of 64
+                                //   (0 = as many as ~1 GB of trajectories and simulated observations allow); tests force the split with it
     // ("hidden_activation" = tanh | relu | sigmoid, "output_activation" = softplus | identity: kept in cude_ctx::net)
     // ---- ablation
     int mixed = 1;              // CUDE_NO_MIXED

@@ -566,6 +566,41 @@ struct BootstrapReduceArgs {
     double* mean; double* sd; int32_t* n_used;
 };
 hipError_t launch_bootstrap_reduce(const BootstrapReduceArgs& a, const int32_t* ranks_dev, hipStream_t s);
+// Prediction discrepancies and npde (cude_npde, cude_npde.hip; the numbered rules in include/cude.h).
+constexpr int kNpdeMaxRows = kMaxObs - 1;         // R = T - 1
+constexpr int32_t kNpdeSingular = 1, kNpdeFew = 2, kNpdeFailedSims = 4, kNpdeBadObs = 8;      // CUDE_NPDE_*
+// Rule 2's sets, or (normals_only) the z alone: out[k][i] over all N subjects
+struct NpdePlaceArgs {
+    int64_t N; int32_t K, normals_only;
+    double prior_mean, prior_sd;
+    uint64_t seed; int64_t subject_offset, first_rep;
+    double* out;                                  // [K][N]
+};
+hipError_t launch_npde_place(const NpdePlaceArgs& a, hipStream_t s);
+// Rule 4 for subjects [subj0, subj0 + n_subj): y[k][r][li] = slab value of (set k, subject li, time r + 1, `state`) +
+// (sigma s) eps, and used[k][li] = every row finite.  slab: [K][n_subj][T][NS] (the multi-set dense-output launch's).  eps:
+// what y held (host noise, uploaded there) or the Philox draw of (subject_offset + subj0 + li, first_rep + k, r).
+// noise_only: y[k][r][li] = eps alone (slab, sigma, used unused).
+struct NpdeObserveArgs {
+    int64_t subj0, n_subj;
+    int32_t K, T, NS, state, from_noise, noise_only;
+    double scale;
+    const double* slab; const double* sigma;      // sigma: [N] of the population
+    double* y; uint8_t* used;                     // [K][T - 1][n_subj], [K][n_subj]
+    uint64_t seed; int64_t subject_offset, first_rep;
+};
+hipError_t launch_npde_observe(const NpdeObserveArgs& a, hipStream_t s);
+// Rules 5 ... 9 over y / used of one pass.  obs: the population's row of (state, t_0), [T][N] from there; outputs [R][N]
+// (n_used, status [N]) at the population's own subject index, any of them null.  n_failed: incremented per subject with
+// SINGULAR, FEW or BAD_OBS.
+struct NpdeReduceArgs {
+    int64_t N, subj0, n_subj;
+    int32_t K, R;
+    const double* y; const uint8_t* used; const double* obs; const double* sigma;
+    double* pred_mean; double* pred_var; double* pd; double* npde;
+    int32_t* below; int32_t* below_decorr; int32_t* n_used; int32_t* status; int32_t* n_failed;
+};
+hipError_t launch_npde_reduce(const NpdeReduceArgs& a, hipStream_t s);
 // per-subject profile-likelihood intervals (cude_profile_intervals, cude_common.hip): the scan's running state, the ends'
 // brackets and the CUDE_CI_* bits of include/cude.h; all arrays [N] unless noted
 constexpr int kProfileWaves = 4;                  // waves of a reduction workgroup: the set dimension is split over them

@@ -66,6 +66,24 @@ __device__ __forceinline__ double rng_bootstrap_normal(uint64_t seed, int64_t su
     return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
 }
 
+// Block kinds 3 and 4, cude_npde's draws (rules 2 and 4 there, cude_npde.hip): the bootstrap's counter with a bit of the row
+// field set that no bootstrap row reaches (its rows stay below 3 * kMaxObs = 96): kRngKindNpdeEta for the random effect of
+// (subject, replicate), kRngKindNpdeNoise | row for the residual draw of (subject, replicate, row < 31).
+constexpr uint32_t kRngKindNpdeEta = kRngKindBootstrap | 0x8000u, kRngKindNpdeNoise = kRngKindBootstrap | 0x4000u;
+__host__ __device__ inline void rng_npde_counter(int64_t subject_global, int64_t rep, uint32_t kind_row, uint32_t (&c)[4]) {
+    c[0] = (uint32_t)(uint64_t)subject_global;
+    c[1] = (uint32_t)((uint64_t)subject_global >> 32);
+    c[2] = (uint32_t)(uint64_t)rep;
+    c[3] = kind_row | ((uint32_t)((uint64_t)rep >> 32) << 16);
+}
+__device__ __forceinline__ double rng_npde_normal(uint64_t seed, int64_t subject_global, int64_t rep, uint32_t kind_row) {
+    uint32_t c[4];
+    rng_npde_counter(subject_global, rep, kind_row, c);
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u1 = u01(c[0], c[1]), u2 = u01(c[2], c[3]);
+    return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+}
+
 // proposal of subject i: state + proposal_std * standard normal (host row z, or the device stream)
 __device__ __forceinline__ double mh_proposal(const double* __restrict__ p, const double* __restrict__ z, const RngKey& key,
                                               double proposal_std, int64_t i) {

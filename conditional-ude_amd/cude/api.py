@@ -1079,6 +1079,35 @@ def bootstrap_conditional(betas, nn, models, timepoints, cpeptide_data, *, sigma
     return _bootstrap(pop.engine, center, sigma, len(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
 
 
+def _npde(eng, sigma, prior_eta, prior_omega, n_sims, seed, samples, noise, state):
+    """The namespace npde / suppression_npde return, from what cude_npde leaves (the context's shared parameters are set)."""
+    if seed is not None and (samples is None or noise is None):
+        eng.set_rng(seed)
+    r = eng.npde(sigma, n_sims, samples, prior_mean=prior_eta, prior_sd=prior_omega, noise=noise, state=state)
+    ok = np.isfinite(r["npde"])
+    pooled = r["npde"][ok]
+    return SimpleNamespace(pd=r["pd"], npde=r["npde"], pred_mean=r["pred_mean"], pred_sd=np.sqrt(r["pred_var"]),
+                           status=r["status"], n_used=r["n_used"],
+                           npde_mean=float(np.mean(pooled)) if pooled.size else float("nan"),
+                           npde_var=float(np.var(pooled, ddof=1)) if pooled.size > 1 else float("nan"))
+
+
+def npde(p_neural, models, timepoints, cpeptide_data, sigma, prior_eta, prior_omega, *, n_sims=1000, seed=None, samples=None,
+         noise=None, n_steps=None):
+    """Simulation-based prediction discrepancies and normalised prediction distribution errors of the fitted population
+    model (cude_npde; Brendel et al. 2006, Comets et al. 2008 -- what Monolix, saemix and NONMEM report after a SAEM fit):
+    n_sims times per subject a random effect eta ~ Normal(prior_eta, prior_omega) is drawn (or taken from samples (n_sims,
+    N)), the c-peptide model is solved at the data's times and residual noise of standard deviation sigma (a number or
+    (N,)) is added (noise (n_sims, T - 1, N) standard normals, or the device's counter-based stream, seeded by `seed` when
+    given); every observation after t_0 is ranked among its simulations -- pd -- and, after the subject's rows are
+    decorrelated by the Cholesky factor of the simulations' covariance, again -- npde = Phi^-1 of that rank.  Under the
+    model the pooled npde are standard normal.  Returns a namespace: pd, npde, pred_mean, pred_sd (T - 1, N), status (N,)
+    NPDE_* bits, n_used (N,), npde_mean, npde_var (pooled over the finite entries)."""
+    pop = _population(models, timepoints, cpeptide_data, n_steps)
+    pop.engine.set_params(p_neural, None)
+    return _npde(pop.engine, sigma, prior_eta, prior_omega, n_sims, seed, samples, noise, 0)
+
+
 # ----------------------------------------------------------------------------- suppression model
 class _SuppPop:
     def __init__(self, data, timepoints, net, lam, n_steps, device):
@@ -1207,6 +1236,16 @@ def suppression_bootstrap(p, args, *, sigma=None, n_reps=200, level=0.95, seed=N
     pop.engine.set_params(p.neural, None)
     center = np.ascontiguousarray(np.asarray(p.theta, dtype=np.float64).reshape(-1))
     return _bootstrap(pop.engine, center, sigma, 3 * len(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
+
+
+def suppression_npde(p, args, sigma, prior_eta, prior_omega, *, state=2, n_sims=1000, seed=None, samples=None, noise=None,
+                     n_steps=None):
+    """npde for the suppression model: args = (prob, individual_data, timepoints, lambda) as suppression_loss, network
+    p.neural, the rows of state `state` (0-based) with residual standard deviation sigma times that state's loss scale."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, None)
+    return _npde(pop.engine, sigma, prior_eta, prior_omega, n_sims, seed, samples, noise, state)
 
 
 def suppression_loss_and_gradient(p, args, *, n_steps=None):

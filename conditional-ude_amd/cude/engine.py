@@ -59,6 +59,8 @@ _REDUCE = C.CFUNCTYPE(C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.
 
 # status codes of Engine.refine_conditional (CUDE_REFINE_* of include/cude.h)
 REFINE_CONVERGED, REFINE_AT_BOUND, REFINE_MAX_EVALS, REFINE_FLAT, REFINE_FAILED = range(5)
+# status bits of Engine.npde (CUDE_NPDE_* of include/cude.h)
+NPDE_SINGULAR, NPDE_FEW, NPDE_FAILED_SIMS, NPDE_BAD_OBS = 1, 2, 4, 8
 # status bits of Engine.profile_intervals (CUDE_CI_* of include/cude.h)
 CI_LOWER_OPEN, CI_UPPER_OPEN, CI_DISCONNECTED, CI_EMPTY, CI_CENTER_FAILED, CI_BELOW_CENTER = 1, 2, 4, 8, 16, 32
 
@@ -629,6 +631,46 @@ class Engine:
         z = np.empty((int(n_reps), self._residual_rows(), self.N))
         check(self._lib.cude_bootstrap_noise(self._h, int(first_rep), int(n_reps), _ptr(z)))
         return z
+
+    def npde(self, sigma, n_sims, cond_sets=None, *, prior_mean=0.0, prior_sd=1.0, noise=None, first_rep=0, state=0,
+             want_decorrelated=True, want_sims=False):
+        """Prediction discrepancies and npde per subject on the device (cude_npde): n_sims simulated data sets per subject --
+        simulate(timepoints) at cond_sets (n_sims, N), or at prior_mean + prior_sd z with z of the device stream of set_rng
+        (None), plus sigma (N,) times the state's scale times standard normals -- against the population's observations of
+        state `state` at the R = T - 1 data times after t_0.  noise (n_sims, R, N), or None: the device stream at replicates
+        first_rep ... (npde_draws returns both kinds of draws).  Returns dict(pred_mean, pred_var, pd (R, N), below (R, N)
+        int32, n_used, status (N,) int32 = NPDE_* bits [, npde (R, N), below_decorr (R, N) int32] [, sims (n_sims, R, N)])."""
+        K, R = int(n_sims), self.T - 1
+        sg = np.ascontiguousarray(np.broadcast_to(_f64(sigma), (self.N,)))
+        cd = None
+        if cond_sets is not None:
+            cd = _f64(cond_sets)
+            if cd.shape != (K, self.N):
+                raise ValueError(f"expected cond_sets ({K}, {self.N})")
+        nz = None
+        if noise is not None:
+            nz = _f64(noise)
+            if nz.shape != (K, R, self.N):
+                raise ValueError(f"expected noise ({K}, {R}, {self.N})")
+        out = {"pred_mean": np.empty((R, self.N)), "pred_var": np.empty((R, self.N)), "pd": np.empty((R, self.N)),
+               "below": np.empty((R, self.N), dtype=np.int32), "n_used": np.empty(self.N, dtype=np.int32),
+               "status": np.empty(self.N, dtype=np.int32)}
+        if want_decorrelated:
+            out["npde"], out["below_decorr"] = np.empty((R, self.N)), np.empty((R, self.N), dtype=np.int32)
+        if want_sims:
+            out["sims"] = np.empty((K, R, self.N))
+        check(self._lib.cude_npde(
+            self._h, K, _ptr(cd), float(prior_mean), float(prior_sd), _ptr(sg), int(first_rep), _ptr(nz), int(state),
+            _ptr(out["pred_mean"]), _ptr(out["pred_var"]), _ptr(out["below"]), _ptr(out.get("below_decorr")), _ptr(out["pd"]),
+            _ptr(out.get("npde")), _ptr(out["n_used"]), _ptr(out["status"]), _ptr(out.get("sims"))))
+        return out
+
+    def npde_draws(self, first_rep, n_sims):
+        """The standard normals npde(cond_sets=None, noise=None, first_rep=first_rep) draws: (eta_normals (n_sims, N), noise
+        (n_sims, T - 1, N))."""
+        z, eps = np.empty((int(n_sims), self.N)), np.empty((int(n_sims), self.T - 1, self.N))
+        check(self._lib.cude_npde_draws(self._h, int(first_rep), int(n_sims), _ptr(z), _ptr(eps)))
+        return z, eps
 
     def mh_chain(self, normals, uniforms, sigma, prior_mean, prior_sd, proposal_std, temperature=1.0, gamma=1.0,
                  n_mc=None):

@@ -30,7 +30,7 @@ export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEMod
        profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
-       curvatures, suppression_curvatures, map_curvature, bootstrap_conditional, suppression_bootstrap,
+       curvatures, suppression_curvatures, map_curvature, bootstrap_conditional, suppression_bootstrap, npde, npde_draws, suppression_npde,
        marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores,
        network_information, n_outputs, lm_candidates, train_lm!
 
@@ -226,6 +226,7 @@ end
 # the same problems by the Newton-type iteration of cude_refine_conditional from the starts x0 (nothing: the context's
 # conditional parameters), one launch in fixed-step mode; returns (x, objective, SSE, info, evals, status = REFINE_*)
 const REFINE_CONVERGED, REFINE_AT_BOUND, REFINE_MAX_EVALS, REFINE_FLAT, REFINE_FAILED = 0, 1, 2, 3, 4
+const NPDE_SINGULAR, NPDE_FEW, NPDE_FAILED_SIMS, NPDE_BAD_OBS = Int32(1), Int32(2), Int32(4), Int32(8)     # status bits of npde
 function refine_conditional(c::Ctx, x0, lower, upper; max_evals = 40, xtol = 1e-7, max_step = 0.5, penalty_weight = 0.0,
                             penalty_center = 0.0)
     x = Vector{Float64}(undef, c.N); obj = similar(x); sse = similar(x); info = similar(x)
@@ -274,6 +275,42 @@ function bootstrap_noise(c::Ctx, first_rep::Integer, n_reps::Integer, rows::Inte
     GC.@preserve z check(ccall((:cude_bootstrap_noise, LIB), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}),
         c.h, Int64(first_rep), Int32(n_reps), z))
     z
+end
+# prediction discrepancies and npde per subject on the device (cude_npde): n_sims simulated data sets per subject --
+# simulate at cond_sets N×n_sims, or at prior_mean + prior_sd z with z of the device stream of set_rng! (nothing), plus
+# sigma[i] times the state's scale times standard normals -- against the population's observations of state `state`
+# (1-based) at the R = T - 1 data times after t₀.  noise N×R×n_sims, or nothing: the device stream at replicates first_rep ...
+# (npde_draws returns both kinds of draws).  Returns (pred_mean, pred_var, pd N×R, below N×R, n_used, status, npde N×R,
+# below_decorr N×R, sims N×R×n_sims); the last three are nothing unless asked for
+function npde(c::Ctx, sigma, n_sims::Integer, rows::Integer; cond_sets = nothing, prior_mean = 0.0, prior_sd = 1.0,
+              noise = nothing, first_rep = 0, state = 1, want_decorrelated = true, want_sims = false)
+    sg = sigma isa Real ? fill(Float64(sigma), c.N) : Vector{Float64}(vec(sigma))
+    cd = cond_sets === nothing ? nothing : Matrix{Float64}(cond_sets)
+    cd === nothing || size(cd) == (c.N, n_sims) || error("cond_sets must be N×n_sims")
+    nz = noise === nothing ? nothing : Array{Float64,3}(noise)
+    nz === nothing || size(nz) == (c.N, rows, n_sims) || error("noise must be N×rows×n_sims")
+    pm = Matrix{Float64}(undef, c.N, rows); pv = similar(pm); pd = similar(pm)
+    below = Matrix{Int32}(undef, c.N, rows)
+    n_used = Vector{Int32}(undef, c.N); status = similar(n_used)
+    nd = want_decorrelated ? similar(pm) : nothing
+    bd = want_decorrelated ? similar(below) : nothing
+    sims = want_sims ? Array{Float64,3}(undef, c.N, rows, n_sims) : nothing
+    GC.@preserve sg cd nz pm pv pd below n_used status nd bd sims check(ccall((:cude_npde, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int32, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        c.h, Int32(n_sims), cd === nothing ? C_NULL : pointer(cd), Float64(prior_mean), Float64(prior_sd), sg,
+        Int64(first_rep), nz === nothing ? C_NULL : pointer(nz), Int32(state - 1), pm, pv, below,
+        bd === nothing ? C_NULL : pointer(bd), pd, nd === nothing ? C_NULL : pointer(nd), n_used, status,
+        sims === nothing ? C_NULL : pointer(sims)))
+    pm, pv, pd, below, n_used, status, nd, bd, sims
+end
+# the standard normals npde(...; cond_sets = nothing, noise = nothing, first_rep) draws: (N×n_sims, N×rows×n_sims)
+function npde_draws(c::Ctx, first_rep::Integer, n_sims::Integer, rows::Integer)
+    z = Matrix{Float64}(undef, c.N, n_sims)
+    eps = Array{Float64,3}(undef, c.N, rows, n_sims)
+    GC.@preserve z eps check(ccall((:cude_npde_draws, LIB), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}),
+        c.h, Int64(first_rep), Int32(n_sims), z, eps))
+    z, eps
 end
 
 # the two ways of solving the per-subject problems behind every frozen-network estimate (keyword `method`): `search` =
@@ -1179,6 +1216,24 @@ function bootstrap_conditional(betas, neural_network_parameters, models, timepoi
     set_params!(c, neural_network_parameters, nothing)
     bootstrap_summary(c, betas, sigma, length(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
 end
+# what npde / suppression_npde return from the context `c` (shared parameters set): pooled over the finite entries
+function npde_summary(c::Ctx, sigma, prior_η, prior_Ω, rows, n_sims, seed, samples, noise, state)
+    seed !== nothing && (samples === nothing || noise === nothing) && set_rng!(c, seed)
+    pm, pv, pd, _, n_used, status, nd, _, _ = npde(c, sigma, n_sims, rows; cond_sets = samples, prior_mean = prior_η,
+        prior_sd = prior_Ω, noise = noise, state = state)
+    pooled = filter(isfinite, vec(nd))
+    m = isempty(pooled) ? NaN : sum(pooled) / length(pooled)
+    v = length(pooled) > 1 ? sum((pooled .- m) .^ 2) / (length(pooled) - 1) : NaN
+    (pd = pd, npde = nd, pred_mean = pm, pred_sd = sqrt.(pv), status = status, n_used = n_used, npde_mean = m, npde_var = v)
+end
+# simulation-based prediction discrepancies and npde of the fitted population model (cude_npde): η ~ Normal(prior_η, prior_Ω)
+# per simulation (or samples N×n_sims), residual noise of standard deviation sigma (noise N×(T-1)×n_sims, or the device stream)
+function npde(p_neural, models, timepoints, cpeptide_data, sigma, prior_η, prior_Ω; n_sims = 1000, seed = nothing,
+              samples = nothing, noise = nothing, n_steps = nothing)
+    c = population(models, timepoints, cpeptide_data; n_steps = n_steps)
+    set_params!(c, p_neural, nothing)
+    npde_summary(c, sigma, prior_η, prior_Ω, length(timepoints) - 1, n_sims, seed, samples, noise, 1)
+end
 
 # ----------------------------------------------------------------------------------------------- suppression model
 struct SuppressionProblem          # stands in for ODEProblem(ude_lsup!, u0, tspan) with the network closed over
@@ -1223,6 +1278,13 @@ function suppression_bootstrap(p, (prob, individual_data, timepoints, λ); sigma
     c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
     set_params!(c, p.neural, nothing)
     bootstrap_summary(c, p.theta, sigma, 3 * length(timepoints), n_reps, level, seed, noise, lower, upper, return_replicates)
+end
+# npde for the suppression model: the rows of state `state` (1-based), sigma times that state's loss scale
+function suppression_npde(p, (prob, individual_data, timepoints, λ), sigma, prior_η, prior_Ω; state = 3, n_sims = 1000,
+                          seed = nothing, samples = nothing, noise = nothing, n_steps = nothing)
+    c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
+    set_params!(c, p.neural, nothing)
+    npde_summary(c, sigma, prior_η, prior_Ω, length(timepoints) - 1, n_sims, seed, samples, noise, state)
 end
 function suppression_loss_and_gradient!(G, p, (prob, individual_data, timepoints, λ))
     c = supp_population(prob, individual_data, timepoints, λ)

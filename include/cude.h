@@ -486,6 +486,64 @@ int32_t cude_predictive_bands(cude_ctx* ctx, int32_t n_sets, const double* cond_
                               int32_t state, int32_t n_ranks, const int32_t* ranks, double* order_out, double* mean_out,
                               int32_t* bad_sets_out);
 
+/* Simulation-based prediction discrepancies pd and their decorrelated, normalised form npde per subject (Brendel et al.
+ * 2006, Comets et al. 2008: what Monolix, saemix and NONMEM report after a SAEM fit), reduced on the device: do the observed
+ * data look like draws from the fitted (network, mu, Omega, sigma)?  The reference has no such diagnostic; the host loop this
+ * replaces is n_sims x (cude_set_params, cude_simulate, a download of the trajectories) and numpy.  The host receives
+ * per-subject rows, never the simulations (unless it asks for them).
+ *   1. Rows: the R = T - 1 data times t_1 ... t_{T-1} of state `state`; t_0 is the initial state and is never drawn.
+ *      C-peptide models: state must be 0, the observed state (the observation is the population's own row).  Suppression
+ *      model: state 0, 1 or 2 (the observation is that state's data row).  R <= 31 (n_obs <= 32).
+ *   2. Random effects: set k uses cond_sets[k] ([n_sims][N] row-major), or with cond_sets == NULL prior_mean + prior_sd z: the
+ *      product rounded, then the sum (no fma); z a standard normal of the context's Philox key (cude_set_rng), counter =
+ *      (global subject, first_rep + k) in a block kind no other entry point uses, Box-Muller as the Metropolis draws.
+ *      2 <= n_sims <= 4096, 0 <= first_rep, first_rep + n_sims <= 2^47.
+ *   3. Solve: set k is solved exactly as cude_predictive_bands rule 1 solves a set at the data's own times: v[k, r, i] has the
+ *      bits of cude_simulate's state `state` at t_{r+1} after cude_set_params(ctx, NULL, cond_sets[k]).
+ *   4. Simulated observation: y_sim[k, r, i] = v[k, r, i] + (sigma[i] s) eps[k, r, i], every operation rounded on its own; s =
+ *      the state's cude_get_scale value (suppression) or 1 (c-peptide).  eps = noise[(k R + r) N + i] ([n_sims][R][N]), or
+ *      with noise == NULL a Philox normal of a second block kind of its own with counter (global subject, first_rep + k,
+ *      row r).  A draw depends on (seed, global subject, replicate, row) alone: not on the chunking, not on the sharding
+ *      (cude_set_rng's subject_offset).  cude_npde_draws returns exactly the normals a call with NULL inputs uses:
+ *      eta_normals_out [n_sims][N] (the z of rule 2), noise_out [n_sims][R][N]; either may be NULL, not both.
+ *   5. Used simulations: a simulation with a non-finite y_sim in any row is left out for that subject; n_used_out[i] counts
+ *      the rest.  sims_out (optional, [n_sims][R][N]) returns y_sim, left-out simulations included.
+ *   6. Moments over the used simulations, in replicate order: m_r = (((y_0r + y_1r) + ...)) / n_used; C_rs = (sum_k
+ *      (y_kr - m_r) (y_ks - m_s)) / (n_used - 1), the sum started at +0.0, each product rounded, then added (no fma).
+ *      pred_mean_out, pred_var_out ([R][N]) = m and the diagonal of C.
+ *   7. pd: below_out[r N + i] = #{k used : y_kr < y_obs_r}, strict and exact; pd_out = below / n_used clipped to
+ *      [1 / (2 n_used), 1 - 1 / (2 n_used)].
+ *   8. Decorrelation: C = L L' row by row, sequential sums without fma: for s < r, L_rs = ((C_rs - L_r0 L_s0) - ... -
+ *      L_r,s-1 L_s,s-1) / L_ss; the pivot p = (C_rr - L_r0^2) - ... - L_r,r-1^2, L_rr = sqrt(p).  A pivot with
+ *      !(p > 2^-40 C_rr) sets CUDE_NPDE_SINGULAR.  w = L^-1 (y - m) by forward substitution, w_r = (((y_r - m_r) - L_r0 w_0) -
+ *      ... - L_r,r-1 w_r-1) / L_rr, for the observation and for every used simulation; below_decorr_out[r N + i] = #{k used
+ *      : w_kr < w_obs_r}; npde_out = Phi^-1(below_decorr / n_used, clipped as pd) by Wichura's AS241 (PPND16), written out in
+ *      the library.
+ *   9. status_out[i], bits: CUDE_NPDE_SINGULAR (below_decorr = -1, npde = NaN; pd is still given); CUDE_NPDE_FEW (n_used <=
+ *      R: treated as singular, the factorisation is not attempted); CUDE_NPDE_FAILED_SIMS (n_used < n_sims);
+ *      CUDE_NPDE_BAD_OBS (a non-finite observation in a row, or a non-finite sigma[i]: every double output NaN, every
+ *      count -1, n_used included).  cude_n_failed afterwards counts the subjects with SINGULAR, FEW or BAD_OBS.  Other
+ *      subjects are unaffected, bit for bit.
+ *  10. All n_sims simulations of a subject are resident when it is reduced: the solves are split over whole workgroups of 64
+ *      subjects by ~1 GB of trajectories and simulated observations (option "npde_subjects" forces the split), and every
+ *      output is bit-identical for every split and every sharding.
+ *  11. CUDE_ERR_UNSUPPORTED for a network on the fallback kernel (cude_set_network), whose dense output takes one parameter
+ *      set; CUDE_ERR_STATE under stream capture, without a population or shared parameters; CUDE_ERR_ARG for n_sims or
+ *      first_rep out of range, a bad state, a null or negative sigma entry, prior_sd not > 0 (or a non-finite prior) while
+ *      cond_sets == NULL, or no output requested.  Leaves the context's parameters and the position of its Metropolis stream
+ *      untouched.  Adaptive mode: cude_adaptive_steps refuses afterwards.
+ * All outputs optional, at least one.  One multi-set dense-output launch per pass, then the reduction; one stream, no
+ * graph, one synchronisation per pass. */
+#define CUDE_NPDE_SINGULAR    1
+#define CUDE_NPDE_FEW         2
+#define CUDE_NPDE_FAILED_SIMS 4
+#define CUDE_NPDE_BAD_OBS     8
+int32_t cude_npde(cude_ctx* ctx, int32_t n_sims, const double* cond_sets, double prior_mean, double prior_sd,
+                  const double* sigma, int64_t first_rep, const double* noise, int32_t state, double* pred_mean_out,
+                  double* pred_var_out, int32_t* below_out, int32_t* below_decorr_out, double* pd_out, double* npde_out,
+                  int32_t* n_used_out, int32_t* status_out, double* sims_out);
+int32_t cude_npde_draws(cude_ctx* ctx, int64_t first_rep, int32_t n_sims, double* eta_normals_out, double* noise_out);
+
 /* The per-set objective of per-subject values and its per-subject argmin -- `likelihood_values` / `map_objective_values`
  * over the kept samples and their `argmax` / `argmin`, from which the MLE / MAP LBFGS runs start
  * (c-peptide/06-saem.jl:226-235).  SSE_i(cond_sets[k][i]) for every set ([n_sets][N] row-major) through
@@ -901,10 +959,11 @@ int32_t cude_xchg_info(cude_ctx* ctx, int32_t* n_ranks, int32_t* rank, int32_t* 
  * "predictive_times" (cude_predictive_bands: subjects per solve launch, rounded up to 64, and output times per launch; 0 =
  * by the ~1 GB budget of sample trajectories; tests force several launches in either dimension with them), "bootstrap_chunk" /
  * "bootstrap_subjects" (cude_bootstrap_conditional: replicates per launch and subjects per pass, rounded up to 64; 0 = by the
- * ~256 MB / ~1 GB budgets; tests force either split with them).  Values are decimal integers as text unless noted.  Every option is also read once
+ * ~256 MB / ~1 GB budgets; tests force either split with them), "npde_subjects" (cude_npde: subjects per pass, rounded up to 64; 0 =
+ * by the ~1 GB budget; tests force the split with it).  Values are decimal integers as text unless noted.  Every option is also read once
  * at cude_create from its environment variable (CUDE_CPEP_PATH, CUDE_CPEP_KEEP, CUDE_SUPP_STORE, CUDE_SUPP_CKPT,
  * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED, CUDE_PROFILE_CHUNK,
- * CUDE_PREDICTIVE_SUBJECTS, CUDE_PREDICTIVE_TIMES, CUDE_BOOTSTRAP_CHUNK, CUDE_BOOTSTRAP_SUBJECTS).
+ * CUDE_PREDICTIVE_SUBJECTS, CUDE_PREDICTIVE_TIMES, CUDE_BOOTSTRAP_CHUNK, CUDE_BOOTSTRAP_SUBJECTS, CUDE_NPDE_SUBJECTS).
  * Options that shape the launch path take effect at the next cude_set_population_*.  No reference line: these are
  * properties of this implementation. */
 int32_t cude_set_option(cude_ctx* ctx, const char* name, const char* value);
