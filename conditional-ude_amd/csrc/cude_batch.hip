@@ -1,6 +1,6 @@
 // libcude_hip.so -- the entry points that batch launches: dense output and predictive bands, conditional sets, marginal
 // likelihoods, subject scores, network information, sensitivities, multi-start evaluation and screening, likelihood
-// profiles and their intervals, per-subject fits and their parametric bootstrap, prediction discrepancies and npde.  Each is its own argument checks, chunking, small kernels and copies
+// profiles and their intervals, per-subject fits and their parametric bootstrap, prediction discrepancies and npde, the visual predictive check by subject group.  Each is its own argument checks, chunking, small kernels and copies
 // around the launches of cude_launch.hip, in chunks sized by cude_select.hip's sets_per_launch.
 #include "cude_ctx.h"
 
@@ -1461,6 +1461,169 @@ int32_t cude_npde_draws(cude_ctx* c, int64_t first_rep, int32_t n_sims, double* 
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
     }
+    return CUDE_OK;
+}
+
+int32_t cude_vpc(cude_ctx* c, int32_t n_sims, const double* cond_sets, double prior_mean, double prior_sd, const double* sigma,
+                 int64_t first_rep, const double* noise, int32_t state, int32_t n_groups, const int32_t* group, int32_t n_levels,
+                 const double* levels, int32_t n_ci, const double* ci_levels, double* obs_q_out, double* sim_ci_out,
+                 double* sim_q_out, int32_t* n_members_out, int32_t* n_sims_used_out, int32_t* status_out) {
+    int32_t rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_pop) return fail(CUDE_ERR_STATE, "population not set");
+    if (!c->have_nn) return fail(CUDE_ERR_STATE, "shared parameters not set");
+    if (c->net.generic())
+        return fail(CUDE_ERR_UNSUPPORTED, "cude_vpc: the network of this context runs on the fallback kernel "
+                                          "(cude_set_network), whose dense output takes one parameter set");
+    if (c->capturing) return fail(CUDE_ERR_STATE, "cude_vpc under stream capture");
+    if (n_sims < 2 || n_sims > cude::kPredMaxSets) return fail(CUDE_ERR_ARG, "need 2 <= n_sims <= 4096");
+    if (first_rep < 0 || first_rep > cude::kRngMaxReplicate - n_sims) return fail(CUDE_ERR_ARG, "need 0 <= first_rep, first_rep + n_sims <= 2^47");
+    const bool cpep = is_cpep(c);
+    const int NS = cpep ? c->cfg.n_state : 3;
+    if (state < 0 || state >= (cpep ? 1 : 3)) return fail(CUDE_ERR_ARG, "state out of range (c-peptide models: 0, the observed state)");
+    if (!cond_sets && (!(prior_sd > 0) || !std::isfinite(prior_sd) || !std::isfinite(prior_mean)))
+        return fail(CUDE_ERR_ARG, "need finite prior_mean and prior_sd > 0 when cond_sets is null");
+    if (!obs_q_out && !sim_ci_out && !sim_q_out) return fail(CUDE_ERR_ARG, "none of obs_q_out, sim_ci_out, sim_q_out requested");
+    if (n_groups < 1 || n_groups > cude::kVpcMaxGroups) return fail(CUDE_ERR_ARG, "need 1 <= n_groups <= 8");
+    const auto increasing = [](int32_t n, const double* q) {
+        if (n < 1 || n > cude::kVpcMaxLevels || !q) return false;
+        for (int i = 0; i < n; i++)
+            if (!(q[i] >= 0.0 && q[i] <= 1.0) || (i > 0 && !(q[i] > q[i - 1]))) return false;
+        return true;
+    };
+    if (!increasing(n_levels, levels)) return fail(CUDE_ERR_ARG, "need 1 <= n_levels <= 8 levels, strictly increasing inside [0, 1]");
+    if (!increasing(n_ci, ci_levels)) return fail(CUDE_ERR_ARG, "need 1 <= n_ci <= 8 ci_levels, strictly increasing inside [0, 1]");
+    if (!sigma) return fail(CUDE_ERR_ARG, "null sigma");
+    const int64_t N = c->N, K = n_sims, nb = c->nblocks;
+    for (int64_t i = 0; i < N; i++) {
+        if (sigma[i] < 0) return fail(CUDE_ERR_ARG, "sigma must not be negative");
+        if (group && group[i] >= n_groups) return fail(CUDE_ERR_ARG, "group id >= n_groups");
+    }
+    const int T = c->T, R = T - 1, P = c->P, G = n_groups, L = n_levels, C = n_ci;
+    if (R < 1) return fail(CUDE_ERR_ARG, "the population has no data time after t_0");
+    // Simulations per pass: as many as ~1 GB of trajectories ([sims][N][T][NS]), simulated observations ([sims][R][N]) and
+    // their flags allow -- all N subjects of a simulation are resident when it is reduced
+    const double per_sim = (8.0 * NS * T + 8.0 * R + 1.0) * (double)nb * cude::kBlock;
+    const int64_t chunk = sets_per_launch(K, 65535, 1e9, per_sim, c->opt.vpc_sims);
+    const size_t GRL = (size_t)G * R * L;
+    DevBuf<double> d_cond, d_slab, d_y, d_part, d_sigma, d_q, d_lev;
+    DevBuf<int32_t> d_int;
+    DevBuf<uint8_t> d_used, d_bad, d_simbad;
+    OutputTables tables;
+    HIP_TRY(d_cond.resize((size_t)chunk * N));
+    HIP_TRY(d_sigma.resize((size_t)N));
+    HIP_TRY(d_slab.resize((size_t)chunk * N * T * NS));
+    HIP_TRY(d_y.resize((size_t)chunk * R * N));
+    HIP_TRY(d_used.resize((size_t)chunk * N));
+    HIP_TRY(d_bad.resize((size_t)N));
+    HIP_TRY(d_simbad.resize((size_t)K * G));
+    if (cpep || adaptive(c)) HIP_TRY(d_part.resize((size_t)chunk * nb * (P + 2)));
+    HIP_TRY(d_q.resize((size_t)(K + 1 + C) * GRL));        // sim_q [K][G][R][L], obs_q [G][R][L], sim_ci [G][R][L][C]
+    HIP_TRY(d_lev.resize((size_t)(L + C)));
+    HIP_TRY(d_int.resize((size_t)3 * N + 2 * G));          // the strata, their member lists, status [N]; n_members, n_used [G]
+    double* const d_simq = d_q.p;
+    double* const d_obsq = d_q.p + (size_t)K * GRL;
+    double* const d_ci = d_obsq + GRL;
+    int32_t* const d_grp = d_int.p;
+    int32_t* const d_members = d_int.p + N;
+    int32_t* const d_status = d_int.p + 2 * N;
+    int32_t* const d_nmem = d_int.p + 3 * N;
+    int32_t* const d_nused = d_nmem + G;
+    const double* const obs = cpep ? c->obs.p : c->data.p + (size_t)state * T * N;
+    // ---- rule 2: the members of every stratum, in subject order (the host knows the ids; the device the observations)
+    HIP_TRY(push(c, d_sigma.p, sigma, N));
+    HIP_TRY(push(c, d_lev.p, levels, L));
+    HIP_TRY(push(c, d_lev.p + L, ci_levels, C));
+    HIP_TRY(cude::launch_vpc_bad_obs(N, R, obs, d_sigma.p, d_bad.p, c->stream));
+    std::vector<uint8_t> bad((size_t)N);
+    HIP_TRY(fetch(c, bad.data(), d_bad.p, N));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int32_t> grp((size_t)N), status((size_t)N), members, first((size_t)G + 1, 0), n_members((size_t)G, 0);
+    for (int64_t i = 0; i < N; i++) {
+        const int32_t g = group ? group[i] : 0;
+        status[(size_t)i] = g < 0 ? CUDE_VPC_NO_GROUP : (bad[(size_t)i] ? CUDE_VPC_BAD_OBS : 0);
+        grp[(size_t)i] = status[(size_t)i] ? -1 : g;
+        if (grp[(size_t)i] >= 0) n_members[(size_t)g]++;
+    }
+    for (int g = 0; g < G; g++) first[(size_t)g + 1] = first[(size_t)g] + n_members[(size_t)g];
+    members.resize((size_t)std::max<int32_t>(1, first[(size_t)G]));
+    {
+        std::vector<int32_t> at(first.begin(), first.end() - 1);
+        for (int64_t i = 0; i < N; i++)
+            if (grp[(size_t)i] >= 0) members[(size_t)at[(size_t)grp[(size_t)i]]++] = (int32_t)i;
+    }
+    HIP_TRY(push(c, d_grp, grp.data(), N));
+    if (first[(size_t)G] > 0) HIP_TRY(push(c, d_members, members.data(), (size_t)first[(size_t)G]));
+    HIP_TRY(push(c, d_status, status.data(), N));
+    HIP_TRY(push(c, d_nmem, n_members.data(), G));
+    HIP_TRY(hipMemsetAsync(d_simbad.p, 0, (size_t)K * G, c->stream));
+    const bool force_select = c->opt.vpc_select != 0;
+    cude::VpcColumnsArgs ca{};
+    ca.N = N; ca.R = R; ca.G = G; ca.L = L; ca.levels = d_lev.p;
+    // ---- rule 4: the observations as one more "simulation" (rows t_1 ... of the population's table [T][N])
+    for (int g = 0; g < G && obs_q_out; g++) {
+        ca.y = obs + N; ca.K = 1; ca.sim_bad = nullptr; ca.out = d_obsq;
+        ca.g = g; ca.members = d_members + first[(size_t)g]; ca.n = n_members[(size_t)g];
+        HIP_TRY(cude::launch_vpc_columns(ca, force_select, c->stream));
+    }
+    // ---- rules 1 and 5, pass by pass
+    if ((rc = tables.upload(c, T, c->tp.data()))) return rc;
+    DenseLaunch d;                                        // a pass's sets at the data's own times; the caller's order of subjects
+    d.cond = d_cond.p; d.partials = d_part.p; d.keep_perm = false;
+    d.traj_ss = 1; d.traj_st = 3; d.traj_sn = 3 * T;
+    d.k0 = 0; d.kn = T;
+    d.traj = d_slab.p; d.set_stride = (int64_t)NS * T * N; d.blk_first = 0; d.blk_count = nb;
+    cude::NpdePlaceArgs pl{};
+    pl.N = N; pl.normals_only = 0; pl.prior_mean = prior_mean; pl.prior_sd = prior_sd;
+    pl.seed = c->rng_seed; pl.subject_offset = c->rng_offset; pl.out = d_cond.p;
+    cude::NpdeObserveArgs oa{};
+    oa.T = T; oa.NS = NS; oa.state = state; oa.from_noise = noise ? 1 : 0;
+    oa.scale = cpep ? 1.0 : c->scale[state];
+    oa.slab = d_slab.p; oa.sigma = d_sigma.p; oa.y = d_y.p; oa.used = d_used.p;
+    oa.seed = c->rng_seed; oa.subject_offset = c->rng_offset;
+    oa.subj0 = 0; oa.n_subj = N;
+    for (int64_t k0 = 0; k0 < K; k0 += chunk) {
+        const int64_t kn = std::min<int64_t>(chunk, K - k0);
+        if (cond_sets) HIP_TRY(push(c, d_cond.p, cond_sets + (size_t)k0 * N, (size_t)kn * N));
+        else {
+            pl.K = (int32_t)kn; pl.first_rep = first_rep + k0;
+            HIP_TRY(cude::launch_npde_place(pl, c->stream));
+        }
+        // outputs a failed adaptive solve does not reach stay NaN
+        if (adaptive(c)) HIP_TRY(hipMemsetAsync(d_slab.p, 0xff, (size_t)kn * d.set_stride * sizeof(double), c->stream));
+        d.n_sets = (int32_t)kn;
+        if ((rc = launch_dense(c, tables, d))) return rc;
+        // the caller's noise of these simulations goes into the table of simulated observations and is turned into them in place
+        if (noise) HIP_TRY(push(c, d_y.p, noise + (size_t)k0 * R * N, (size_t)kn * R * N));
+        oa.K = (int32_t)kn; oa.first_rep = first_rep + k0;
+        HIP_TRY(cude::launch_npde_observe(oa, c->stream));
+        HIP_TRY(cude::launch_vpc_flag(N, (int)kn, G, d_grp, d_used.p, d_simbad.p + (size_t)k0 * G, d_status, c->stream));
+        for (int g = 0; g < G; g++) {
+            ca.y = d_y.p; ca.K = (int32_t)kn; ca.sim_bad = d_simbad.p + (size_t)k0 * G; ca.out = d_simq + (size_t)k0 * GRL;
+            ca.g = g; ca.members = d_members + first[(size_t)g]; ca.n = n_members[(size_t)g];
+            HIP_TRY(cude::launch_vpc_columns(ca, force_select, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));         // the slab, the sets and the tables are the next pass's too
+    }
+    // ---- rule 6
+    HIP_TRY(cude::launch_vpc_count((int)K, G, d_simbad.p, d_nused, c->stream));
+    if (sim_ci_out) {
+        cude::VpcIntervalArgs ia{};
+        ia.sim_q = d_simq; ia.sim_bad = d_simbad.p; ia.n_used = d_nused; ia.n_members = d_nmem;
+        ia.K = (int32_t)K; ia.G = G; ia.R = R; ia.L = L; ia.C = C; ia.ci_levels = d_lev.p + L; ia.ci = d_ci;
+        HIP_TRY(cude::launch_vpc_interval(ia, c->stream));
+    }
+    HIP_TRY(fetch(c, obs_q_out, d_obsq, GRL));
+    HIP_TRY(fetch(c, sim_ci_out, d_ci, GRL * C));
+    HIP_TRY(fetch(c, sim_q_out, d_simq, (size_t)K * GRL));
+    HIP_TRY(fetch(c, n_sims_used_out, d_nused, G));
+    HIP_TRY(fetch(c, status.data(), d_status, N));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t failed = 0;
+    for (int64_t i = 0; i < N; i++) failed += (status[(size_t)i] & (CUDE_VPC_BAD_OBS | CUDE_VPC_FAILED_SIMS)) != 0;
+    c->last_failed = failed;
+    if (n_members_out) std::memcpy(n_members_out, n_members.data(), (size_t)G * sizeof(int32_t));
+    if (status_out) std::memcpy(status_out, status.data(), (size_t)N * sizeof(int32_t));
     return CUDE_OK;
 }
 

@@ -216,6 +216,8 @@ const OptionEntry kOptions[] = {
     {"bootstrap_chunk", "CUDE_BOOTSTRAP_CHUNK", &Options::bootstrap_chunk, false, false},
     {"bootstrap_subjects", "CUDE_BOOTSTRAP_SUBJECTS", &Options::bootstrap_subjects, false, false},
     {"npde_subjects", "CUDE_NPDE_SUBJECTS", &Options::npde_subjects, false, false},
+    {"vpc_sims", "CUDE_VPC_SIMS", &Options::vpc_sims, false, false},
+    {"vpc_select", "CUDE_VPC_SELECT", &Options::vpc_select, false, false},
 };
 }  // namespace
 

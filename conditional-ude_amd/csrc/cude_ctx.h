@@ -105,6 +105,10 @@ struct Options {
                                 //   64 (0 = as many as ~1 GB of replicate results allow); tests force either split with them
     int npde_subjects = 0;      // "npde_subjects" / CUDE_NPDE_SUBJECTS: subjects per pass of cude_npde, rounded up to whole workgroups of 64
                                 //   (0 = as many as ~1 GB of trajectories and simulated observations allow); tests force the split with it
+    int vpc_sims = 0;           // "vpc_sims" / CUDE_VPC_SIMS: simulations per pass of cude_vpc (0 = as many as ~1 GB of trajectories and
+                                //   simulated observations allow); tests force the split with it
+    int vpc_select = 0;         // "vpc_select" / CUDE_VPC_SELECT (tests): 1 = every column of cude_vpc's reduction over subjects goes
+                                //   through the radix select, whatever its length
     // ("hidden_activation" = tanh | relu | sigmoid, "output_activation" = softplus | identity: kept in cude_ctx::net)
     // ---- ablation
     int mixed = 1;              // CUDE_NO_MIXED

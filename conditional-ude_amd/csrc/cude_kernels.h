@@ -601,6 +601,38 @@ struct NpdeReduceArgs {
     int32_t* below; int32_t* below_decorr; int32_t* n_used; int32_t* status; int32_t* n_failed;
 };
 hipError_t launch_npde_reduce(const NpdeReduceArgs& a, hipStream_t s);
+// Visual predictive check by subject group (cude_vpc, cude_vpc.hip; the numbered rules in include/cude.h).
+constexpr int kVpcMaxGroups = 8, kVpcMaxLevels = 8;
+constexpr int32_t kVpcNoGroup = 1, kVpcFailedSims = 2, kVpcBadObs = 4;      // CUDE_VPC_*
+// bad[i] = 1: a non-finite observation in a row of obs ([T][N] from the row of t_0), or a non-finite sigma[i]
+hipError_t launch_vpc_bad_obs(int64_t N, int R, const double* obs, const double* sigma, uint8_t* bad, hipStream_t s);
+// Rule 5's left-out simulations of a pass: grp [N] = the stratum a subject counts in (< 0: none), used [K][N]
+// (launch_npde_observe's).  sim_bad[k * G + g] = 1 and status[i] |= kVpcFailedSims where a member's simulation is not used.
+hipError_t launch_vpc_flag(int64_t N, int K, int G, const int32_t* grp, const uint8_t* used, uint8_t* sim_bad, int32_t* status,
+                           hipStream_t s);
+// Rule 3 across the n members of ONE group: column (k, r) is y[(k R + r) N + members[j]], j < n; out[((k G + g) R + r) L + l]
+// = its quantile at levels[l] (NaN where n == 0 or sim_bad[k * G + g]; sim_bad may be null).  n <= 4096: the sorting tile,
+// unless force_select; longer columns: the radix select, one workgroup per column.
+struct VpcColumnsArgs {
+    const double* y; int64_t N;
+    const int32_t* members; int32_t n;
+    int32_t K, R, G, g, L;
+    const double* levels;                         // [L] on the device
+    const uint8_t* sim_bad;                       // [K][G] of this pass, or null
+    double* out;                                  // [K][G][R][L] of this pass
+};
+hipError_t launch_vpc_columns(const VpcColumnsArgs& a, bool force_select, hipStream_t s);
+// n_used[g] = the simulations of sim_bad [K][G] that are not flagged
+hipError_t launch_vpc_count(int K, int G, const uint8_t* sim_bad, int32_t* n_used, hipStream_t s);
+// Rule 6: ci[((g R + r) L + l) C + c] = rule 3 at ci_levels[c] over the n_used[g] used values sim_q[., g, r, l] (NaN where
+// n_members[g] == 0 or n_used[g] == 0)
+struct VpcIntervalArgs {
+    const double* sim_q; const uint8_t* sim_bad; const int32_t* n_used; const int32_t* n_members;
+    int32_t K, G, R, L, C;
+    const double* ci_levels;                      // [C] on the device
+    double* ci;
+};
+hipError_t launch_vpc_interval(const VpcIntervalArgs& a, hipStream_t s);
 // per-subject profile-likelihood intervals (cude_profile_intervals, cude_common.hip): the scan's running state, the ends'
 // brackets and the CUDE_CI_* bits of include/cude.h; all arrays [N] unless noted
 constexpr int kProfileWaves = 4;                  // waves of a reduction workgroup: the set dimension is split over them

@@ -1108,6 +1108,54 @@ def npde(p_neural, models, timepoints, cpeptide_data, sigma, prior_eta, prior_om
     return _npde(pop.engine, sigma, prior_eta, prior_omega, n_sims, seed, samples, noise, 0)
 
 
+def _vpc_groups(groups, N):
+    """(ids (N,) int32 or None, number of groups, labels or None): integer ids as they are (negative = left out), anything
+    else mapped to 0, 1, ... in order of first appearance."""
+    if groups is None:
+        return None, 1, None
+    g = np.asarray(groups).reshape(-1)
+    if g.shape != (N,):
+        raise ValueError(f"expected groups ({N},)")
+    if np.issubdtype(g.dtype, np.integer):
+        return g.astype(np.int32), max(1, int(g.max()) + 1), None
+    labels = list(dict.fromkeys(g.tolist()))
+    index = {v: k for k, v in enumerate(labels)}
+    return np.array([index[v] for v in g.tolist()], dtype=np.int32), len(labels), labels
+
+
+def _vpc(eng, sigma, prior_eta, prior_omega, groups, levels, ci, n_sims, seed, samples, noise, state):
+    """The namespace vpc / suppression_vpc return, from what cude_vpc leaves (the context's shared parameters are set)."""
+    if seed is not None and (samples is None or noise is None):
+        eng.set_rng(seed)
+    ids, G, labels = _vpc_groups(groups, eng.N)
+    r = eng.vpc(sigma, n_sims, samples, prior_mean=prior_eta, prior_sd=prior_omega, noise=noise, state=state, groups=ids,
+                n_groups=G, levels=levels, ci_levels=ci, want_sim_q=False)
+    obs, band = r["observed"], r["simulated_ci"]
+    with np.errstate(invalid="ignore"):
+        outside = (obs < band[..., 0]) | (obs > band[..., -1])
+    return SimpleNamespace(observed=obs, simulated_ci=band, outside=outside, n_members=r["n_members"],
+                           n_sims_used=r["n_sims_used"], status=r["status"], levels=np.asarray(levels, dtype=np.float64),
+                           ci_levels=np.asarray(ci, dtype=np.float64), labels=labels)
+
+
+def vpc(p_neural, models, timepoints, cpeptide_data, sigma, prior_eta, prior_omega, *, groups=None, levels=(0.05, 0.5, 0.95),
+        ci=(0.025, 0.5, 0.975), n_sims=1000, seed=None, samples=None, noise=None, n_steps=None):
+    """Visual predictive check of the fitted population model by subject group (cude_vpc -- the diagnostic Monolix, saemix,
+    NONMEM/PsN and nlmixr plot after a SAEM fit; the reference stratifies its figures by NGT / IGT / T2DM,
+    `train_data.types`): n_sims data sets are simulated exactly as npde simulates them (eta ~ Normal(prior_eta, prior_omega)
+    or samples (n_sims, N); residual noise of standard deviation sigma, from noise (n_sims, T - 1, N) or the device's stream,
+    seeded by `seed` when given).  Inside each group the type-7 quantiles ACROSS SUBJECTS at `levels` are taken of every
+    simulated data set and of the observations at every data time after t_0, and of each simulated quantile the quantiles
+    at `ci` across the simulations.  groups: (N,) integer ids (negative = left out), or labels (e.g. the reference's type
+    strings) mapped to ids in order of first appearance and returned as `labels`; None = one group.  Returns a namespace:
+    observed (G, T - 1, L), simulated_ci (G, T - 1, L, C), outside (G, T - 1, L) -- the observed quantile lies below the
+    first or above the last `ci` level of its simulated counterpart --, n_members, n_sims_used (G,), status (N,) VPC_* bits,
+    levels, ci_levels, labels."""
+    pop = _population(models, timepoints, cpeptide_data, n_steps)
+    pop.engine.set_params(p_neural, None)
+    return _vpc(pop.engine, sigma, prior_eta, prior_omega, groups, levels, ci, n_sims, seed, samples, noise, 0)
+
+
 # ----------------------------------------------------------------------------- suppression model
 class _SuppPop:
     def __init__(self, data, timepoints, net, lam, n_steps, device):
@@ -1246,6 +1294,16 @@ def suppression_npde(p, args, sigma, prior_eta, prior_omega, *, state=2, n_sims=
     pop = _supp_population(prob, data, timepoints, lam, n_steps)
     pop.engine.set_params(p.neural, None)
     return _npde(pop.engine, sigma, prior_eta, prior_omega, n_sims, seed, samples, noise, state)
+
+
+def suppression_vpc(p, args, sigma, prior_eta, prior_omega, *, state=2, groups=None, levels=(0.05, 0.5, 0.95),
+                    ci=(0.025, 0.5, 0.975), n_sims=1000, seed=None, samples=None, noise=None, n_steps=None):
+    """vpc for the suppression model: args = (prob, individual_data, timepoints, lambda) as suppression_loss, network
+    p.neural, the rows of state `state` (0-based) with residual standard deviation sigma times that state's loss scale."""
+    prob, data, timepoints, lam = args
+    pop = _supp_population(prob, data, timepoints, lam, n_steps)
+    pop.engine.set_params(p.neural, None)
+    return _vpc(pop.engine, sigma, prior_eta, prior_omega, groups, levels, ci, n_sims, seed, samples, noise, state)
 
 
 def suppression_loss_and_gradient(p, args, *, n_steps=None):

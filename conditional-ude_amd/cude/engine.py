@@ -61,6 +61,8 @@ _REDUCE = C.CFUNCTYPE(C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.
 REFINE_CONVERGED, REFINE_AT_BOUND, REFINE_MAX_EVALS, REFINE_FLAT, REFINE_FAILED = range(5)
 # status bits of Engine.npde (CUDE_NPDE_* of include/cude.h)
 NPDE_SINGULAR, NPDE_FEW, NPDE_FAILED_SIMS, NPDE_BAD_OBS = 1, 2, 4, 8
+# status bits of Engine.vpc (CUDE_VPC_* of include/cude.h)
+VPC_NO_GROUP, VPC_FAILED_SIMS, VPC_BAD_OBS = 1, 2, 4
 # status bits of Engine.profile_intervals (CUDE_CI_* of include/cude.h)
 CI_LOWER_OPEN, CI_UPPER_OPEN, CI_DISCONNECTED, CI_EMPTY, CI_CENTER_FAILED, CI_BELOW_CENTER = 1, 2, 4, 8, 16, 32
 
@@ -671,6 +673,45 @@ class Engine:
         z, eps = np.empty((int(n_sims), self.N)), np.empty((int(n_sims), self.T - 1, self.N))
         check(self._lib.cude_npde_draws(self._h, int(first_rep), int(n_sims), _ptr(z), _ptr(eps)))
         return z, eps
+
+    def vpc(self, sigma, n_sims, cond_sets=None, *, prior_mean=0.0, prior_sd=1.0, noise=None, first_rep=0, state=0,
+            groups=None, n_groups=None, levels=(0.05, 0.5, 0.95), ci_levels=(0.025, 0.5, 0.975), want_sim_q=True):
+        """Visual predictive check by subject group on the device (cude_vpc): n_sims data sets simulated as npde simulates
+        them (the same arguments, the same bits); inside each group (groups (N,) int ids in [0, n_groups), negative = left
+        out; None: one group) the type-7 quantiles across subjects at `levels` of every simulated data set and of the
+        observations at every data time after t_0, then the quantiles at `ci_levels` across the simulations.  Returns
+        dict(observed (G, R, L), simulated_ci (G, R, L, C) [, simulated_q (n_sims, G, R, L)], n_members, n_sims_used (G,)
+        int32, status (N,) int32 = VPC_* bits)."""
+        K, R = int(n_sims), self.T - 1
+        sg = np.ascontiguousarray(np.broadcast_to(_f64(sigma), (self.N,)))
+        cd = None
+        if cond_sets is not None:
+            cd = _f64(cond_sets)
+            if cd.shape != (K, self.N):
+                raise ValueError(f"expected cond_sets ({K}, {self.N})")
+        nz = None
+        if noise is not None:
+            nz = _f64(noise)
+            if nz.shape != (K, R, self.N):
+                raise ValueError(f"expected noise ({K}, {R}, {self.N})")
+        gr = None
+        if groups is not None:
+            gr = np.ascontiguousarray(np.asarray(groups, dtype=np.int32).reshape(-1))
+            if gr.shape != (self.N,):
+                raise ValueError(f"expected groups ({self.N},)")
+        G = int(n_groups) if n_groups is not None else (1 if gr is None else max(1, int(gr.max()) + 1))
+        lv, cv = _f64(levels).reshape(-1), _f64(ci_levels).reshape(-1)
+        L, C_ = lv.size, cv.size
+        out = {"observed": np.empty((G, R, L)), "simulated_ci": np.empty((G, R, L, C_)),
+               "n_members": np.empty(G, dtype=np.int32), "n_sims_used": np.empty(G, dtype=np.int32),
+               "status": np.empty(self.N, dtype=np.int32)}
+        if want_sim_q:
+            out["simulated_q"] = np.empty((K, G, R, L))
+        check(self._lib.cude_vpc(
+            self._h, K, _ptr(cd), float(prior_mean), float(prior_sd), _ptr(sg), int(first_rep), _ptr(nz), int(state),
+            G, _ptr(gr), L, _ptr(lv), C_, _ptr(cv), _ptr(out["observed"]), _ptr(out["simulated_ci"]),
+            _ptr(out.get("simulated_q")), _ptr(out["n_members"]), _ptr(out["n_sims_used"]), _ptr(out["status"])))
+        return out
 
     def mh_chain(self, normals, uniforms, sigma, prior_mean, prior_sd, proposal_std, temperature=1.0, gamma=1.0,
                  n_mc=None):

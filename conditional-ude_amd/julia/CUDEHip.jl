@@ -30,7 +30,7 @@ export chain, neural_network_model, CPeptideConditionalUDEModel, CPeptideCUDEMod
        profile_confidence_intervals,
        SuppressionProblem, suppression_loss, simul, fit_suppression_model, simulate, individual_log_likelihood, SAEM,
        sensitivities, suppression_sensitivities, conditional_standard_errors, wald_confidence_intervals,
-       curvatures, suppression_curvatures, map_curvature, bootstrap_conditional, suppression_bootstrap, npde, npde_draws, suppression_npde,
+       curvatures, suppression_curvatures, map_curvature, bootstrap_conditional, suppression_bootstrap, npde, npde_draws, suppression_npde, vpc, suppression_vpc,
        marginal_likelihood, gauss_hermite_rule, grid_rule, information_criteria, em_updates, subject_scores,
        network_information, n_outputs, lm_candidates, train_lm!
 
@@ -227,6 +227,7 @@ end
 # conditional parameters), one launch in fixed-step mode; returns (x, objective, SSE, info, evals, status = REFINE_*)
 const REFINE_CONVERGED, REFINE_AT_BOUND, REFINE_MAX_EVALS, REFINE_FLAT, REFINE_FAILED = 0, 1, 2, 3, 4
 const NPDE_SINGULAR, NPDE_FEW, NPDE_FAILED_SIMS, NPDE_BAD_OBS = Int32(1), Int32(2), Int32(4), Int32(8)     # status bits of npde
+const VPC_NO_GROUP, VPC_FAILED_SIMS, VPC_BAD_OBS = Int32(1), Int32(2), Int32(4)                           # status bits of vpc
 function refine_conditional(c::Ctx, x0, lower, upper; max_evals = 40, xtol = 1e-7, max_step = 0.5, penalty_weight = 0.0,
                             penalty_center = 0.0)
     x = Vector{Float64}(undef, c.N); obj = similar(x); sse = similar(x); info = similar(x)
@@ -311,6 +312,38 @@ function npde_draws(c::Ctx, first_rep::Integer, n_sims::Integer, rows::Integer)
     GC.@preserve z eps check(ccall((:cude_npde_draws, LIB), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}),
         c.h, Int64(first_rep), Int32(n_sims), z, eps))
     z, eps
+end
+
+# visual predictive check by subject group on the device (cude_vpc): n_sims data sets simulated as npde simulates them (the
+# same arguments, the same bits); inside each group (groups: N ids in 0:n_groups-1, negative = left out; nothing: one
+# group) the type-7 quantiles across subjects at `levels` of every simulated data set and of the observations at the R = T - 1
+# data times after t₀, then the quantiles at `ci_levels` across the simulations.  Returns (observed L×R×G, simulated_ci
+# C×L×R×G, simulated_q L×R×G×n_sims or nothing, n_members, n_sims_used, status = VPC_* bits)
+function vpc(c::Ctx, sigma, n_sims::Integer, rows::Integer; cond_sets = nothing, prior_mean = 0.0, prior_sd = 1.0,
+             noise = nothing, first_rep = 0, state = 1, groups = nothing, n_groups = nothing, levels = (0.05, 0.5, 0.95),
+             ci_levels = (0.025, 0.5, 0.975), want_sim_q = true)
+    sg = sigma isa Real ? fill(Float64(sigma), c.N) : Vector{Float64}(vec(sigma))
+    cd = cond_sets === nothing ? nothing : Matrix{Float64}(cond_sets)
+    cd === nothing || size(cd) == (c.N, n_sims) || error("cond_sets must be N×n_sims")
+    nz = noise === nothing ? nothing : Array{Float64,3}(noise)
+    nz === nothing || size(nz) == (c.N, rows, n_sims) || error("noise must be N×rows×n_sims")
+    gr = groups === nothing ? nothing : Vector{Int32}(vec(groups))
+    gr === nothing || length(gr) == c.N || error("groups must have N entries")
+    G = n_groups !== nothing ? Int(n_groups) : (gr === nothing ? 1 : max(1, Int(maximum(gr)) + 1))
+    lv = collect(Float64, levels); cv = collect(Float64, ci_levels)
+    L = length(lv); C = length(cv)
+    obs_q = Array{Float64,3}(undef, L, rows, G)
+    sim_ci = Array{Float64,4}(undef, C, L, rows, G)
+    sim_q = want_sim_q ? Array{Float64,4}(undef, L, rows, G, n_sims) : nothing
+    n_members = Vector{Int32}(undef, G); n_used = similar(n_members); status = Vector{Int32}(undef, c.N)
+    GC.@preserve sg cd nz gr lv cv obs_q sim_ci sim_q n_members n_used status check(ccall((:cude_vpc, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Int32,
+         Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+        c.h, Int32(n_sims), cd === nothing ? C_NULL : pointer(cd), Float64(prior_mean), Float64(prior_sd), sg,
+        Int64(first_rep), nz === nothing ? C_NULL : pointer(nz), Int32(state - 1), Int32(G),
+        gr === nothing ? C_NULL : pointer(gr), Int32(L), lv, Int32(C), cv, obs_q, sim_ci,
+        sim_q === nothing ? C_NULL : pointer(sim_q), n_members, n_used, status))
+    obs_q, sim_ci, sim_q, n_members, n_used, status
 end
 
 # the two ways of solving the per-subject problems behind every frozen-network estimate (keyword `method`): `search` =
@@ -1235,6 +1268,37 @@ function npde(p_neural, models, timepoints, cpeptide_data, sigma, prior_η, prio
     npde_summary(c, sigma, prior_η, prior_Ω, length(timepoints) - 1, n_sims, seed, samples, noise, 1)
 end
 
+# group ids of vpc / suppression_vpc: integers as they are (negative = left out), anything else mapped to 0, 1, ... in order of
+# first appearance; (ids or nothing, number of groups, labels or nothing)
+function vpc_groups(groups, N)
+    groups === nothing && return nothing, 1, nothing
+    length(groups) == N || error("groups must have N entries")
+    eltype(groups) <: Integer && return Vector{Int32}(vec(groups)), max(1, Int(maximum(groups)) + 1), nothing
+    labels = unique(vec(groups))
+    Int32[findfirst(==(g), labels) - 1 for g in vec(groups)], length(labels), labels
+end
+# what vpc / suppression_vpc return from the context `c` (shared parameters set)
+function vpc_summary(c::Ctx, sigma, prior_η, prior_Ω, rows, groups, levels, ci, n_sims, seed, samples, noise, state)
+    seed !== nothing && (samples === nothing || noise === nothing) && set_rng!(c, seed)
+    ids, G, labels = vpc_groups(groups, c.N)
+    obs, band, _, n_members, n_used, status = vpc(c, sigma, n_sims, rows; cond_sets = samples, prior_mean = prior_η,
+        prior_sd = prior_Ω, noise = noise, state = state, groups = ids, n_groups = G, levels = levels, ci_levels = ci,
+        want_sim_q = false)
+    outside = (obs .< band[1, :, :, :]) .| (obs .> band[end, :, :, :])
+    (observed = obs, simulated_ci = band, outside = outside, n_members = n_members, n_sims_used = n_used, status = status,
+     levels = collect(Float64, levels), ci_levels = collect(Float64, ci), labels = labels)
+end
+# visual predictive check of the fitted population model by subject group (cude_vpc): the simulations of npde; inside each
+# group the quantiles across subjects at `levels` of every simulated data set and of the observations, and of each simulated
+# quantile the quantiles at `ci` across the simulations.  groups: N integer ids (negative = left out) or labels (the
+# reference's `train_data.types`), nothing = one group.  observed L×(T-1)×G, simulated_ci C×L×(T-1)×G, outside L×(T-1)×G
+function vpc(p_neural, models, timepoints, cpeptide_data, sigma, prior_η, prior_Ω; groups = nothing, levels = (0.05, 0.5, 0.95),
+             ci = (0.025, 0.5, 0.975), n_sims = 1000, seed = nothing, samples = nothing, noise = nothing, n_steps = nothing)
+    c = population(models, timepoints, cpeptide_data; n_steps = n_steps)
+    set_params!(c, p_neural, nothing)
+    vpc_summary(c, sigma, prior_η, prior_Ω, length(timepoints) - 1, groups, levels, ci, n_sims, seed, samples, noise, 1)
+end
+
 # ----------------------------------------------------------------------------------------------- suppression model
 struct SuppressionProblem          # stands in for ODEProblem(ude_lsup!, u0, tspan) with the network closed over
     network::Chain
@@ -1285,6 +1349,14 @@ function suppression_npde(p, (prob, individual_data, timepoints, λ), sigma, pri
     c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
     set_params!(c, p.neural, nothing)
     npde_summary(c, sigma, prior_η, prior_Ω, length(timepoints) - 1, n_sims, seed, samples, noise, state)
+end
+# vpc for the suppression model: the rows of state `state` (1-based), sigma times that state's loss scale
+function suppression_vpc(p, (prob, individual_data, timepoints, λ), sigma, prior_η, prior_Ω; state = 3, groups = nothing,
+                         levels = (0.05, 0.5, 0.95), ci = (0.025, 0.5, 0.975), n_sims = 1000, seed = nothing,
+                         samples = nothing, noise = nothing, n_steps = nothing)
+    c = supp_population(prob, individual_data, timepoints, λ; n_steps = n_steps)
+    set_params!(c, p.neural, nothing)
+    vpc_summary(c, sigma, prior_η, prior_Ω, length(timepoints) - 1, groups, levels, ci, n_sims, seed, samples, noise, state)
 end
 function suppression_loss_and_gradient!(G, p, (prob, individual_data, timepoints, λ))
     c = supp_population(prob, individual_data, timepoints, λ)

@@ -544,6 +544,61 @@ int32_t cude_npde(cude_ctx* ctx, int32_t n_sims, const double* cond_sets, double
                   int32_t* n_used_out, int32_t* status_out, double* sims_out);
 int32_t cude_npde_draws(cude_ctx* ctx, int64_t first_rep, int32_t n_sims, double* eta_normals_out, double* noise_out);
 
+/* Visual predictive check by subject group (what Monolix, saemix, NONMEM/PsN and nlmixr plot after a SAEM fit; the
+ * reference stratifies what it plots by NGT / IGT / T2DM, `train_data.types`), reduced on the device: n_sims data sets are
+ * simulated from the fitted (network, mu, Omega, sigma); inside each stratum of subjects the quantiles ACROSS SUBJECTS of
+ * every simulated data set are taken at every data time, then an interval across the simulations of each such quantile,
+ * next to the same quantiles of the observed data.  The host route this replaces is cude_npde(..., sims_out), a download
+ * of [n_sims][R][N] doubles and numpy.quantile over subjects, then over simulations.
+ *   1. Simulation: rows, random effects, solve and simulated observations are cude_npde's rules 1 ... 4 word for word: with
+ *      the same context, seed, first_rep, cond_sets, noise, sigma and state, y_sim[k, r, i] has the bits of cude_npde's
+ *      sims_out.  2 <= n_sims <= 4096, R = T - 1 <= 31.
+ *   2. Groups: group[i] in [0, n_groups) is subject i's stratum (group == NULL: everybody in group 0), 1 <= n_groups <= 8.
+ *      A negative id leaves the subject out of every stratum and sets CUDE_VPC_NO_GROUP (alone: such a subject is not
+ *      looked at further); an id >= n_groups is CUDE_ERR_ARG.  A subject with a non-finite observation in any row, or a
+ *      non-finite sigma[i], is left out of its group throughout and gets CUDE_VPC_BAD_OBS.  n_members_out[g] counts the
+ *      subjects that remain: the members.
+ *   3. Quantile of n values at level q (type 7: Julia's `quantile`, numpy.quantile's default): h = (n - 1) q in double,
+ *      lo = floor(h), hi = min(lo + 1, n - 1), g = h - lo, d = x_hi - x_lo; the value is x_hi - d (1 - g) when g >= 1/2,
+ *      otherwise x_lo + d g, every operation rounded on its own (no fma).  x_lo, x_hi are exact order statistics: values of
+ *      the column, selected and not computed.  Where a column holds both -0.0 and +0.0 the sign of a selected zero is
+ *      unspecified.  levels [n_levels] and ci_levels [n_ci] are strictly increasing inside [0, 1], 1 <= n_levels <= 8,
+ *      1 <= n_ci <= 8.
+ *   4. Observed quantiles: obs_q_out[(g R + r) L + l] = rule 3 at levels[l] over the observations of group g's members in
+ *      row r (L = n_levels).
+ *   5. Simulated quantiles: sim_q_out[((k G + g) R + r) L + l] = the same quantile of y_sim[k, r, .] over group g's members
+ *      (G = n_groups).  A simulation in which any member of group g has a non-finite y_sim in any row is left out for that
+ *      group: its sim_q entries are NaN in every row and level, and that member gets CUDE_VPC_FAILED_SIMS.
+ *      n_sims_used_out[g] counts the simulations that remain (n_sims for a group without members: none is left out).  Other
+ *      groups are unaffected, bit for bit.
+ *   6. Interval across simulations: sim_ci_out[((g R + r) L + l) C + c] = rule 3 at ci_levels[c] over the n_sims_used[g] used
+ *      values sim_q[., g, r, l] (C = n_ci).  A group with no member or no used simulation has NaN in all its double outputs.
+ *   7. status_out[i]: the CUDE_VPC_* bits.  cude_n_failed afterwards counts the subjects with BAD_OBS or FAILED_SIMS.  All N
+ *      subjects of a simulation are resident when it is reduced: the passes are split over simulations by ~1 GB of
+ *      trajectories and simulated observations (option "vpc_sims" forces the simulations per pass), and every output is
+ *      bit-identical for every split.
+ *   8. CUDE_ERR_UNSUPPORTED for a network on the fallback kernel (cude_set_network), as cude_npde; CUDE_ERR_STATE under stream
+ *      capture, without a population or shared parameters; CUDE_ERR_ARG for n_sims, first_rep, n_groups, n_levels or n_ci
+ *      out of range, levels that do not increase strictly inside [0, 1], a group id >= n_groups, a bad state, a null or
+ *      negative sigma entry, prior_sd not > 0 (or a non-finite prior) while cond_sets == NULL, or none of obs_q_out,
+ *      sim_ci_out, sim_q_out requested.  Leaves the context's parameters and the position of its Metropolis stream
+ *      untouched.  Adaptive mode: cude_adaptive_steps refuses afterwards.
+ *   9. The quantiles are over the context's OWN subjects: no exchange is used, a sharded population gets shard-local strata
+ *      (gather the shards' sims through cude_npde if population-wide strata are wanted).
+ * All outputs optional, at least one of the first three.  Per pass one multi-set dense-output launch, the observations, and
+ * per group one selection launch: columns of at most 4096 members on the shared sorting tile, longer ones through a radix
+ * select that works from the column in device memory (option "vpc_select" = 1: every column; tests).  One stream, no graph,
+ * one synchronisation per pass. */
+#define CUDE_VPC_NO_GROUP    1
+#define CUDE_VPC_FAILED_SIMS 2
+#define CUDE_VPC_BAD_OBS     4
+int32_t cude_vpc(cude_ctx* ctx, int32_t n_sims, const double* cond_sets, double prior_mean, double prior_sd,
+                 const double* sigma, int64_t first_rep, const double* noise, int32_t state,
+                 int32_t n_groups, const int32_t* group, int32_t n_levels, const double* levels,
+                 int32_t n_ci, const double* ci_levels,
+                 double* obs_q_out, double* sim_ci_out, double* sim_q_out,
+                 int32_t* n_members_out, int32_t* n_sims_used_out, int32_t* status_out);
+
 /* The per-set objective of per-subject values and its per-subject argmin -- `likelihood_values` / `map_objective_values`
  * over the kept samples and their `argmax` / `argmin`, from which the MLE / MAP LBFGS runs start
  * (c-peptide/06-saem.jl:226-235).  SSE_i(cond_sets[k][i]) for every set ([n_sets][N] row-major) through
@@ -960,10 +1015,12 @@ int32_t cude_xchg_info(cude_ctx* ctx, int32_t* n_ranks, int32_t* rank, int32_t* 
  * by the ~1 GB budget of sample trajectories; tests force several launches in either dimension with them), "bootstrap_chunk" /
  * "bootstrap_subjects" (cude_bootstrap_conditional: replicates per launch and subjects per pass, rounded up to 64; 0 = by the
  * ~256 MB / ~1 GB budgets; tests force either split with them), "npde_subjects" (cude_npde: subjects per pass, rounded up to 64; 0 =
- * by the ~1 GB budget; tests force the split with it).  Values are decimal integers as text unless noted.  Every option is also read once
+ * by the ~1 GB budget; tests force the split with it), "vpc_sims" (cude_vpc: simulations per pass; 0 = by the ~1 GB budget;
+ * tests force the split with it), "vpc_select" (tests: 1 = every column of cude_vpc's reduction over subjects goes through
+ * the radix select).  Values are decimal integers as text unless noted.  Every option is also read once
  * at cude_create from its environment variable (CUDE_CPEP_PATH, CUDE_CPEP_KEEP, CUDE_SUPP_STORE, CUDE_SUPP_CKPT,
  * CUDE_TAPE_STEPS, CUDE_NO_EXPTAB, CUDE_NO_MS_SPLIT, CUDE_NO_AUTO_REGROUP, CUDE_NO_POLL_PINNED, CUDE_DEBUG_SELECTOR, CUDE_ALLOW_PLAIN_MAILBOX, CUDE_XCHG_FAIL_KINDS, CUDE_MH_SPEC, CUDE_FIT_SPEC, CUDE_NO_ADAPTIVE_TEAM, CUDE_DENSE_CHUNK, CUDE_DENSE_LAYOUT, CUDE_REFINE_FUSED, CUDE_PROFILE_CHUNK,
- * CUDE_PREDICTIVE_SUBJECTS, CUDE_PREDICTIVE_TIMES, CUDE_BOOTSTRAP_CHUNK, CUDE_BOOTSTRAP_SUBJECTS, CUDE_NPDE_SUBJECTS).
+ * CUDE_PREDICTIVE_SUBJECTS, CUDE_PREDICTIVE_TIMES, CUDE_BOOTSTRAP_CHUNK, CUDE_BOOTSTRAP_SUBJECTS, CUDE_NPDE_SUBJECTS, CUDE_VPC_SIMS, CUDE_VPC_SELECT).
  * Options that shape the launch path take effect at the next cude_set_population_*.  No reference line: these are
  * properties of this implementation. */
 int32_t cude_set_option(cude_ctx* ctx, const char* name, const char* value);
