@@ -14,6 +14,7 @@
 //     subject walks its column in replicate order (count, plain sum, second pass for the sd); the tile is sorted by the
 //     network cude_predictive.hip sorts with (cude_tilesort.h), +Inf last, and the ranks below n_used are read off.
 #include "cude_kernels.h"
+#include "cude_observe.h"
 #include "cude_rng.h"
 #include "cude_tilesort.h"
 
@@ -23,15 +24,7 @@ namespace {
 constexpr int kGenThreads = 256;
 constexpr int kRefFailedStatus = 4;               // CUDE_REFINE_FAILED
 
-// rule 2: yhat + (sigma s) eps, every operation rounded on its own (no contraction), so that numpy's expression has the
-// same bits and a caller can rebuild a replicate's data from public outputs
-__device__ __forceinline__ double bootstrap_observation(double yhat, double sigma, double scale, double eps) {
-#pragma clang fp contract(off)
-    const double amp = sigma * scale;
-    const double d = amp * eps;
-    return yhat + d;
-}
-// rule 5's second pass, likewise: ss + (v - mean) (v - mean)
+// rule 5's second pass, every operation rounded on its own (as rule 2's, cude_observe.h): ss + (v - mean) (v - mean)
 __device__ __forceinline__ double bootstrap_square_add(double ss, double v, double mean) {
 #pragma clang fp contract(off)
     const double d = v - mean;
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(kGenThreads) void bootstrap_generate_kernel(Bootstr
         return;
     }
     const double yhat = a.traj[s + (int64_t)a.traj_states * (t + (int64_t)a.T * i)];
-    out[q] = bootstrap_observation(yhat, a.sigma[i], a.scale[s], eps);
+    out[q] = simulated_observation(yhat, a.sigma[i], a.scale[s], eps);      // rule 2
 }
 
 __global__ __launch_bounds__(kTileSortThreads) void bootstrap_reduce_kernel(BootstrapReduceArgs a, const int32_t* __restrict__ ranks,
@@ -68,15 +61,13 @@ __global__ __launch_bounds__(kTileSortThreads) void bootstrap_reduce_kernel(Boot
     const int tid = threadIdx.x;
     const int C = 1 << lgC;
     const int64_t q0 = (int64_t)blockIdx.x * C;   // first subject of the tile
-    const int n_el = Kp << lgC;
     const double inf = __builtin_huge_val();
-    for (int idx = tid; idx < n_el; idx += kTileSortThreads) {
-        const int cc = idx & (C - 1), k = idx >> lgC;
+    tile_fill(s_v, C, lgC, Kp, tid, [&](int k, int cc) {
         const int64_t q = q0 + cc;
         double v = inf;
         if (k < a.K && q < a.n_subj && a.status[(int64_t)k * a.stride + q] != kRefFailedStatus) v = a.reps[(int64_t)k * a.stride + q];
-        s_v[idx] = v;
-    }
+        return v;
+    });
     __syncthreads();
     // ---- one lane per subject, in replicate order
     if (tid < C) {
@@ -138,18 +129,7 @@ hipError_t launch_bootstrap_reduce(const BootstrapReduceArgs& a, const int32_t* 
     if (a.K < 1 || a.K > kPredMaxSets || a.n_ranks < 0 || a.n_subj < 1 || !a.reps || !a.status || !a.n_used ||
         (a.n_ranks > 0 && (!a.order || !ranks_dev)))
         return hipErrorInvalidValue;
-    int C = 0;
-    const size_t lds = tile_sort_lds_bytes(a.K, &C);
-    int lgC = 0, Kp = 1;
-    while ((1 << lgC) < C) lgC++;
-    while (Kp < a.K) Kp <<= 1;
-    const int64_t tiles = (a.n_subj + C - 1) / C;
-    // (the largest tile and the kernel's static bytes together pass the 64 KiB a launch may use unasked)
-    const hipError_t attr = hipFuncSetAttribute((const void*)bootstrap_reduce_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)(sizeof(double) * kTileSortDoubles));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(bootstrap_reduce_kernel, dim3((unsigned)tiles), dim3(kTileSortThreads), lds, s, a, ranks_dev, lgC, Kp);
-    return hipGetLastError();
+    return tile_launch(bootstrap_reduce_kernel, tile_geometry(a.K), a.n_subj, s, a, ranks_dev);
 }
 
 }  // namespace cude

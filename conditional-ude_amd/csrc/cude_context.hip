@@ -1,6 +1,6 @@
 // libcude_hip.so -- host side of the C ABI declared in include/cude.h: contexts, populations, parameters.
 // Owns the device-resident population (subject-major SoA), the solver tables and the HIP stream; the launches are in
-// cude_launch.hip (their shapes: cude_select.hip; batches of them: cude_batch.hip, cude_mh.hip), the optimisers in cude_optimise.hip, the multi-GPU exchange in cude_comm.hip.
+// cude_launch.hip (their shapes: cude_select.hip; batches of them: cude_batch.hip, cude_replicates.hip, cude_mh.hip), the optimisers in cude_optimise.hip, the multi-GPU exchange in cude_comm.hip.
 #include <algorithm>
 
 #include "cude_ctx.h"

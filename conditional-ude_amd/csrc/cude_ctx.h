@@ -3,6 +3,7 @@
 //   cude_select.hip    the measured rules that pick a launch shape (one-lane / time-split / mixed, sets per launch, depths)
 //   cude_launch.hip    the launches themselves (ensemble, parameter sets, tangent, dense output) and the entry points that are one
 //   cude_batch.hip     the entry points that batch such launches (simulate, bands, profiles, fits, scores, screening)
+//   cude_replicates.hip  the entry points that simulate replicates of the data (bootstrap, npde, vpc, their draws)
 //   cude_mh.hip        the Metropolis driver (cude_mh_estep, cude_mh_chain)
 //   cude_optimise.hip  Adam (single steps and captured runs), L-BFGS on host vectors
 //   cude_train.hip     restarts trained side by side with their optimiser state on the device (cude_train_restarts)
@@ -26,6 +27,7 @@
 #include "../../include/cude.h"
 #include "cude_kernels.h"
 #include "cude_optim.h"
+#include "cude_passes.h"
 
 namespace cude {
 namespace api {
@@ -426,6 +428,25 @@ struct DenseLaunch {
     int64_t blk_first = 0, blk_count = 0;       // workgroups [blk_first, blk_first + blk_count) of the population (0: all)
 };
 int32_t launch_dense(cude_ctx* c, const OutputTables& tables, const DenseLaunch& d);
+// Simulate and observe (cude_npde, cude_vpc; cude_replicates.hip): what a call's passes share.  The caller's arguments, and
+// the device side that prepare() allocates for passes of at most sets_max simulations of sub_max subjects in `blocks`
+// workgroups: the sets [sets][N], sigma [N] (uploaded), the trajectories [sets][subjects][T][NS] at the data's own times
+// (whose tables it uploads), the simulated observations y [sets][T - 1][subjects] and their flags used [sets][subjects].
+struct SimObserve {
+    const double* cond_sets = nullptr;  // host [n_sims][N]; null: drawn on the device around (prior_mean, prior_sd)
+    double prior_mean = 0.0, prior_sd = 0.0;
+    const double* noise = nullptr;      // host [n_sims][T - 1][N]; null: drawn on the device
+    int64_t first_rep = 0;
+    int32_t state = 0;
+    DevBuf<double> d_cond, d_sigma, d_slab, d_y, d_part;
+    DevBuf<uint8_t> d_used;
+    OutputTables tables;
+    int32_t prepare(cude_ctx* c, const double* sigma, int64_t sets_max, int64_t sub_max, int64_t blocks);
+};
+// One pass, queued: simulations [k0, k0 + kn) of subjects [s0, s0 + sn), s0 a multiple of the workgroup's 64.  With
+// `place` the sets are uploaded or drawn first (all N subjects of them); then the 0xff fill of adaptive mode, the solve, the
+// caller's noise into y, the observations.  The pass's results start at the heads of slab, y and used.
+int32_t simulate_observe_pass(cude_ctx* c, const SimObserve& v, int64_t s0, int64_t sn, int64_t k0, int64_t kn, bool place);
 // ---- cude_batch.hip
 // The device half of cude_network_information, shared with the Levenberg-Marquardt entry points (cude_lm.hip).
 struct InfoRequest {
@@ -443,6 +464,10 @@ struct InfoTables {
     int32_t failed = 0;                 // its host copy: final after the next synchronisation of the stream
 };
 int32_t info_pass(cude_ctx* c, const InfoRequest& rq, InfoTables& tb);
+// The per-subject fits in their stepped form and their search state, shared with the bootstrap (cude_replicates.hip)
+hipError_t refine_stepped(cude_ctx* c, const cude::RefineCfg& k, const cude::RefineArrays& r, double* sse_t, double* score_t,
+                          double* info_t, const double* obs_ov);
+int32_t refine_state(cude_ctx* c, cude::RefineArrays& r, double** sse_t, double** score_t, double** info_t);
 // ---- cude_optimise.hip
 void drop_graph(cude_ctx* c);
 int32_t ensure_trace(cude_ctx* c, int64_t n);

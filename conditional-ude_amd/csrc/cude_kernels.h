@@ -759,7 +759,6 @@ struct PredictiveArgs {
     uint8_t* bad; int64_t bad_stride;            // bad[subject * bad_stride + k] = 1: set k of the subject held a non-finite value
 };
 hipError_t launch_predictive_select(const PredictiveArgs& a, const int32_t* ranks_dev, hipStream_t s);
-size_t predictive_lds_bytes(int K, int* tile_cols);
 // bad_sets[i] = number of flagged sets of subject i
 hipError_t launch_predictive_count(int64_t N, int K, const uint8_t* bad, int32_t* bad_sets, hipStream_t s);
 hipError_t launch_fill(int64_t N, double v, double* out, hipStream_t s);

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "cude_kernels.h"
+#include "cude_observe.h"
 #include "cude_rng.h"
 
 namespace cude {
@@ -31,20 +32,11 @@ constexpr int kNpdeTileBytes = 65536;
 constexpr int kNpdeMaxCols = 64;
 constexpr double kNpdePivotTol = 9.094947017729282379150390625e-13;       // 2^-40
 
-__device__ __forceinline__ bool npde_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
-
 // rule 2: prior_mean + prior_sd z, the product rounded, then the sum
 __device__ __forceinline__ double npde_effect(double mean, double sd, double z) {
 #pragma clang fp contract(off)
     const double d = sd * z;
     return mean + d;
-}
-// rule 4: v + (sigma s) eps, every operation rounded on its own
-__device__ __forceinline__ double npde_observation(double v, double sigma, double scale, double eps) {
-#pragma clang fp contract(off)
-    const double amp = sigma * scale;
-    const double d = amp * eps;
-    return v + d;
 }
 // rule 6: acc + (a - ma) (b - mb)
 __device__ __forceinline__ double npde_cross_add(double acc, double a, double ma, double b, double mb) {
@@ -130,9 +122,9 @@ __global__ __launch_bounds__(kNpdeThreads) void npde_observe_kernel(NpdeObserveA
     for (int r = 0; r < R; r++) {
         const double eps = a.from_noise ? y[(int64_t)r * a.n_subj]
                                         : rng_npde_normal(a.seed, a.subject_offset + i, a.first_rep + k, kRngKindNpdeNoise | (uint32_t)r);
-        const double ys = npde_observation(v[(int64_t)(r + 1) * a.NS], sigma, a.scale, eps);
+        const double ys = simulated_observation(v[(int64_t)(r + 1) * a.NS], sigma, a.scale, eps);      // rule 4
         y[(int64_t)r * a.n_subj] = ys;
-        ok = ok && npde_finite(ys);
+        ok = ok && finite_value(ys);
     }
     a.used[(int64_t)k * a.n_subj + li] = ok ? 1 : 0;
 }
@@ -163,8 +155,8 @@ __global__ __launch_bounds__(kNpdeThreads) void npde_reduce_kernel(NpdeReduceArg
     if (tid < C) {
         int32_t st = 0;
         if (tid < nc) {
-            bool ok = npde_finite(a.sigma[a.subj0 + q0 + tid]);
-            for (int r = 0; r < R; r++) ok = ok && npde_finite(s_w[r * C + tid]);
+            bool ok = finite_value(a.sigma[a.subj0 + q0 + tid]);
+            for (int r = 0; r < R; r++) ok = ok && finite_value(s_w[r * C + tid]);
             if (!ok) st = kNpdeBadObs;
         }
         s_st[tid] = st;

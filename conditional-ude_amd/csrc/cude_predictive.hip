@@ -20,13 +20,13 @@
 #include <hip/hip_runtime.h>
 
 #include "cude_kernels.h"
+#include "cude_observe.h"
 #include "cude_tilesort.h"
 
 namespace cude {
 
 namespace {
 constexpr int kPredThreads = kTileSortThreads;
-constexpr int kPredTileDoubles = kTileSortDoubles;     // 64 KiB
 constexpr int kPredMaxCols = kTileSortMaxCols;
 
 __global__ __launch_bounds__(kPredThreads) void predictive_select_kernel(PredictiveArgs a, const int32_t* __restrict__ ranks,
@@ -38,6 +38,8 @@ __global__ __launch_bounds__(kPredThreads) void predictive_select_kernel(Predict
     const int64_t q0 = (int64_t)blockIdx.x * C;     // first column of the tile
     const int n_el = Kp << lgC;
     const double inf = __builtin_huge_val();
+    // (tile_fill's loop, kept here in its own words: through tile_fill this kernel compiles to one scalar move more than
+    // before, profiles/replicates_split.txt)
     for (int idx = tid; idx < n_el; idx += kPredThreads) {
         const int cc = idx & (C - 1), k = idx >> lgC;
         const int64_t q = q0 + cc;
@@ -52,12 +54,12 @@ __global__ __launch_bounds__(kPredThreads) void predictive_select_kernel(Predict
             const int64_t subj = a.subj0 + q / a.Tc;
             uint8_t* const flag = a.bad + subj * a.bad_stride;
             double acc = s_v[tid];
-            if (!(fabs(acc) <= 1.79769313486231570815e308)) { bad = true; flag[0] = 1; }
+            if (!finite_value(acc)) { bad = true; flag[0] = 1; }
 #pragma unroll 8
             for (int k = 1; k < a.K; k++) {
                 const double v = s_v[(k << lgC) + tid];
                 acc = acc + v;
-                if (!(fabs(v) <= 1.79769313486231570815e308)) { bad = true; flag[k] = 1; }
+                if (!finite_value(v)) { bad = true; flag[k] = 1; }
             }
             if (a.mean != nullptr)
                 a.mean[a.t0 + q % a.Tc + (int64_t)a.n_times * subj] = bad ? __builtin_nan("") : acc / (double)a.K;
@@ -85,26 +87,11 @@ __global__ void predictive_count_kernel(int64_t N, int K, const uint8_t* __restr
 }
 }  // namespace
 
-// LDS of one workgroup and the columns of its tile
-size_t predictive_lds_bytes(int K, int* tile_cols) { return tile_sort_lds_bytes(K, tile_cols); }
-
 // ranks_dev: [n_ranks] on the device, validated by the caller
 hipError_t launch_predictive_select(const PredictiveArgs& a, const int32_t* ranks_dev, hipStream_t s) {
     if (a.K < 1 || a.K > kPredMaxSets || a.n_ranks < 0 || a.n_ranks > kPredMaxRanks || a.n_cols < 1 || a.Tc < 1)
         return hipErrorInvalidValue;
-    int C = 0;
-    const size_t lds = predictive_lds_bytes(a.K, &C);
-    int lgC = 0, Kp = 1;
-    while ((1 << lgC) < C) lgC++;
-    while (Kp < a.K) Kp <<= 1;
-    const int64_t tiles = (a.n_cols + C - 1) / C;
-    // (the largest tile and the kernel's 256 static bytes together pass the 64 KiB a launch may use unasked)
-    const hipError_t attr = hipFuncSetAttribute((const void*)predictive_select_kernel,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)(sizeof(double) * kPredTileDoubles));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(predictive_select_kernel, dim3((unsigned)tiles), dim3(kPredThreads), lds, s, a, ranks_dev, lgC, Kp);
-    return hipGetLastError();
+    return tile_launch(predictive_select_kernel, tile_geometry(a.K), a.n_cols, s, a, ranks_dev);
 }
 
 hipError_t launch_predictive_count(int64_t N, int K, const uint8_t* bad, int32_t* bad_sets, hipStream_t s) {

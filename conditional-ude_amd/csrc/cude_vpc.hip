@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cude_kernels.h"
+#include "cude_observe.h"
 #include "cude_tilesort.h"
 
 namespace cude {
@@ -38,8 +39,6 @@ namespace {
 constexpr int kVpcThreads = kTileSortThreads;
 constexpr int kVpcBatch = 4;                      // elements a lane of the select kernel fetches before it counts them
 constexpr int kVpcTileMax = kPredMaxSets;        // the longest column the sorting tile takes (4096: two columns per tile)
-
-__device__ __forceinline__ bool vpc_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
 
 // rule 3's position of level q among n values
 __device__ __forceinline__ void vpc_rank(int n, double q, int* lo, int* hi, double* frac) {
@@ -78,8 +77,8 @@ __global__ __launch_bounds__(kVpcThreads) void vpc_bad_obs_kernel(int64_t N, int
                                                                   const double* __restrict__ sigma, uint8_t* __restrict__ bad) {
     const int64_t i = (int64_t)blockIdx.x * kVpcThreads + threadIdx.x;
     if (i >= N) return;
-    bool ok = vpc_finite(sigma[i]);
-    for (int r = 0; r < R; r++) ok = ok && vpc_finite(obs[(int64_t)(r + 1) * N + i]);
+    bool ok = finite_value(sigma[i]);
+    for (int r = 0; r < R; r++) ok = ok && finite_value(obs[(int64_t)(r + 1) * N + i]);
     bad[i] = ok ? 0 : 1;
 }
 
@@ -118,13 +117,11 @@ __global__ __launch_bounds__(kVpcThreads) void vpc_tile_kernel(VpcColumnsArgs a,
     const int C = 1 << lgC;
     const int n_cols = a.K * a.R;
     const int q0 = blockIdx.x * C;                   // first column of the tile: column q = k R + r
-    const int n_el = Kp << lgC;
     const double inf = __builtin_huge_val();
-    for (int idx = tid; idx < n_el; idx += kVpcThreads) {
-        const int cc = idx & (C - 1), e = idx >> lgC;
+    tile_fill(s_v, C, lgC, Kp, tid, [&](int e, int cc) {
         const int q = q0 + cc;
-        s_v[idx] = (e < a.n && q < n_cols) ? a.y[(int64_t)q * a.N + a.members[e]] : inf;
-    }
+        return (e < a.n && q < n_cols) ? a.y[(int64_t)q * a.N + a.members[e]] : inf;
+    });
     tile_sort_ascending(s_v, lgC, Kp, tid);          // (cude_tilesort.h; its first step is a barrier)
     for (int idx = tid; idx < a.L << lgC; idx += kVpcThreads) {
         const int l = idx % a.L, cc = idx / a.L;
@@ -275,15 +272,13 @@ __global__ __launch_bounds__(kVpcThreads) void vpc_interval_kernel(VpcIntervalAr
     const int TC = 1 << lgC;
     const int RL = a.R * a.L, n_cols = a.G * RL;     // column q = (g R + r) L + l
     const int q0 = blockIdx.x * TC;
-    const int n_el = Kp << lgC;
     const double inf = __builtin_huge_val();
-    for (int idx = tid; idx < n_el; idx += kVpcThreads) {
-        const int cc = idx & (TC - 1), k = idx >> lgC;
+    tile_fill(s_v, TC, lgC, Kp, tid, [&](int k, int cc) {
         const int q = q0 + cc;
         double v = inf;
         if (k < a.K && q < n_cols && a.sim_bad[(int64_t)k * a.G + q / RL] == 0) v = a.sim_q[(int64_t)k * n_cols + q];
-        s_v[idx] = v;
-    }
+        return v;
+    });
     tile_sort_ascending(s_v, lgC, Kp, tid);
     for (int idx = tid; idx < a.C << lgC; idx += kVpcThreads) {
         const int c = idx % a.C, cc = idx / a.C;
@@ -300,17 +295,6 @@ __global__ __launch_bounds__(kVpcThreads) void vpc_interval_kernel(VpcIntervalAr
         }
         a.ci[(int64_t)q * a.C + c] = v;
     }
-}
-
-// the tile of columns of `len` values: lg of its columns, its padded length, its LDS
-size_t vpc_tile(int len, int* lgC, int* Kp) {
-    int C = 0;
-    const size_t lds = tile_sort_lds_bytes(len, &C);
-    *lgC = 0;
-    *Kp = 1;
-    while ((1 << *lgC) < C) (*lgC)++;
-    while (*Kp < len) *Kp <<= 1;
-    return lds;
 }
 }  // namespace
 
@@ -340,13 +324,7 @@ hipError_t launch_vpc_columns(const VpcColumnsArgs& a, bool force_select, hipStr
     } else if (a.n > kVpcTileMax || force_select) {
         hipLaunchKernelGGL(vpc_select_kernel, dim3((unsigned)n_cols), dim3(kVpcThreads), 0, s, a);
     } else {
-        int lgC = 0, Kp = 1;
-        const size_t lds = vpc_tile(a.n, &lgC, &Kp);
-        const hipError_t attr = hipFuncSetAttribute((const void*)vpc_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    (int)(sizeof(double) * kTileSortDoubles));
-        if (attr != hipSuccess) return attr;
-        const int tiles = (n_cols + (1 << lgC) - 1) >> lgC;
-        hipLaunchKernelGGL(vpc_tile_kernel, dim3((unsigned)tiles), dim3(kVpcThreads), lds, s, a, lgC, Kp);
+        return tile_launch(vpc_tile_kernel, tile_geometry(a.n), n_cols, s, a);
     }
     return hipGetLastError();
 }
@@ -362,15 +340,7 @@ hipError_t launch_vpc_interval(const VpcIntervalArgs& a, hipStream_t s) {
         a.L > kVpcMaxLevels || a.C < 1 || a.C > kVpcMaxLevels || !a.sim_q || !a.sim_bad || !a.n_used || !a.n_members ||
         !a.ci_levels || !a.ci)
         return hipErrorInvalidValue;
-    int lgC = 0, Kp = 1;
-    const size_t lds = vpc_tile(a.K, &lgC, &Kp);
-    const hipError_t attr = hipFuncSetAttribute((const void*)vpc_interval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)(sizeof(double) * kTileSortDoubles));
-    if (attr != hipSuccess) return attr;
-    const int n_cols = a.G * a.R * a.L;
-    const int tiles = (n_cols + (1 << lgC) - 1) >> lgC;
-    hipLaunchKernelGGL(vpc_interval_kernel, dim3((unsigned)tiles), dim3(kVpcThreads), lds, s, a, lgC, Kp);
-    return hipGetLastError();
+    return tile_launch(vpc_interval_kernel, tile_geometry(a.K), a.G * a.R * a.L, s, a);
 }
 
 }  // namespace cude

@@ -307,7 +307,8 @@ def test_null_context_returns_a_status():
 
 def test_one_statement_of_the_rule_and_of_the_sort():
     """The replicate kernels call the refinement's own device statements, and the reduction sorts with the network the
-    predictive bands sort with: neither is restated."""
+    predictive bands sort with: neither is restated.  Nor are the tile's geometry, launch and fill, the simulated
+    observation and the finiteness test of the kernels around the replicate simulations."""
     csrc = os.path.join(ROOT, "conditional-ude_amd", "csrc")
     refine = open(os.path.join(csrc, "cude_refine.hip")).read()
     assert refine.count("void refine_update(") == 1 and refine.count("refine_update(") == 6       # definition + 5 callers
@@ -319,6 +320,36 @@ def test_one_statement_of_the_rule_and_of_the_sort():
     pred = open(os.path.join(csrc, "cude_predictive.hip")).read()
     assert "tile_sort_ascending(" in boot and "tile_sort_ascending(" in pred
     assert "x[u] > y[u]" not in boot and "x[u] > y[u]" not in pred
+    # the frame of the four kernels on the sorting tile is cude_tilesort.h's: each sorts with tile_sort_ascending and is
+    # launched by tile_launch on tile_geometry; bootstrap_reduce_kernel, vpc_tile_kernel and vpc_interval_kernel fill the
+    # tile with tile_fill and spell no fill loop of their own.  predictive_select_kernel may keep its loop -- through
+    # tile_fill it compiled to one scalar move more than before (profiles/replicates_split.txt, "Device code"), and a
+    # kernel whose instruction count grows keeps its own words -- or call tile_fill: one of the two, not both.
+    vpc = open(os.path.join(csrc, "cude_vpc.hip")).read()
+    tile = open(os.path.join(csrc, "cude_tilesort.h")).read()
+    assert tile.count("void tile_fill(") == 1 and tile.count("const int cc = idx & (C - 1), e = idx >> lgC;") == 1
+    may_keep_its_loop = {"predictive_select_kernel"}
+    for kernel, src in (("predictive_select_kernel", pred), ("bootstrap_reduce_kernel", boot), ("vpc_tile_kernel", vpc),
+                        ("vpc_interval_kernel", vpc)):
+        body = src[src.index(f"void {kernel}("):]
+        body = body[:body.index("\n}\n")]
+        assert body.count("tile_sort_ascending(") == 1, kernel
+        fill = body[:body.index("tile_sort_ascending(")]
+        own = fill.count("idx & (C - 1)") + fill.count("idx & (TC - 1)")
+        assert own == 0 or (own == 1 and kernel in may_keep_its_loop), kernel
+        assert fill.count("tile_fill(") == 1 - own, kernel
+        assert src.count(f"tile_launch({kernel}, tile_geometry(") == 1, kernel
+    for src in (pred, boot, vpc):
+        assert "hipFuncSetAttribute" not in src and "while (" not in src[src.index("hipError_t launch_"):]
+    # the simulated observation v + (sigma s) eps has one definition, which both generate / observe kernels call; so has the
+    # finiteness test of these files
+    obs = open(os.path.join(csrc, "cude_observe.h")).read()
+    npde = open(os.path.join(csrc, "cude_npde.hip")).read()
+    assert obs.count("double simulated_observation(") == 1 and obs.count("bool finite_value(") == 1
+    assert "#pragma clang fp contract(off)" in obs[obs.index("double simulated_observation("):]
+    assert boot.count("simulated_observation(") == 1 and npde.count("simulated_observation(") == 1
+    for src in (pred, boot, npde, vpc):
+        assert "amp * eps" not in src and "1.79769313486231570815e308" not in src
 
 
 # ----------------------------------------------------------------------------- the new translation unit

@@ -35,7 +35,7 @@ def tile_constants():
 
 
 def tile_geometry(K):
-    """tile_sort_lds_bytes restated: (Kp, C) of a tile of K values per column."""
+    """tile_geometry restated: (Kp, C) of a tile of K values per column."""
     _, doubles, max_cols = tile_constants()
     Kp = 1
     while Kp < K:

@@ -1,5 +1,5 @@
 """Bit-for-bit comparison of two builds of libcude_hip.so through every entry point that batches launches
-(csrc/cude_batch.hip, csrc/cude_mh.hip): one fresh process per library writes every output array of seeded calls to an
+(csrc/cude_batch.hip, csrc/cude_replicates.hip, csrc/cude_mh.hip): one fresh process per library writes every output array of seeded calls to an
 .npz, a third step compares the two files with numpy.array_equal (NaN positions included).
 
     python tools/compare_entry_points.py run <libcude_hip.so> <out.npz>      # once per library (selects cude._lib.LIB_PATH)
@@ -8,7 +8,11 @@
 Covered: c-peptide populations (2-6-6-1) of 57 and 700 subjects, time-split (30 steps) and one lane per subject
 (cpep_path = 1) with 3 states, adaptive with the 2 states that mode integrates; the suppression model (4-3x5-1, 57
 subjects), fixed step and adaptive.  Every entry point runs with the default chunking and again with the chunk options forcing several launches; mh_chain runs 11 steps for
-gamma in {1, 0.35} x mh_spec in {0, 2, -1} with the caller's draws, mh_estep with the device's.  A call the library
+gamma in {1, 0.35} x mh_spec in {0, 2, -1} with the caller's draws, mh_estep with the device's.  The replicate simulations
+run 9 replicates / simulations: bootstrap_conditional with ranks, with the caller's noise and with the device's draws,
+bootstrap_noise, npde and vpc (3 groups, one subject left out) with the caller's sets and noise and with the device's draws,
+npde_draws; the chunked round splits them by bootstrap_chunk = 2, bootstrap_subjects = npde_subjects = 64, vpc_sims = 2 and
+sends every vpc column through the radix select (vpc_select = 1).  A call the library
 refuses is recorded by its message, which must agree as well."""
 import os
 import sys
@@ -81,6 +85,15 @@ def run(lib_path, out_path):
         cov = np.eye(P) * 0.01 + 0.001
         z, u = rng.standard_normal((11, N)), rng.random((11, N))
         nodes, logw = np.array([-1.7, -0.6, 0.0, 0.6, 1.7]), np.log(np.array([0.05, 0.25, 0.4, 0.25, 0.05]))
+        # the replicate simulations: 9 replicates / simulations, 3 groups with one subject left out
+        rep_rng = np.random.default_rng(2024 + N)
+        B, R = 9, len(tp) - 1
+        sigma = 0.05 * (1.0 + rep_rng.random(N))
+        boot_noise = rep_rng.standard_normal((B, eng._residual_rows(), N))
+        sim_sets = cond[None, :] + 0.3 * rep_rng.standard_normal((B, N))
+        sim_noise = rep_rng.standard_normal((B, R, N))
+        groups = (np.arange(N) % 3).astype(np.int32)
+        groups[N // 2] = -1
 
         def candidates(first, count):
             r = np.random.default_rng(1000 + first)
@@ -88,7 +101,9 @@ def run(lib_path, out_path):
 
         for chunked in (False, True):
             tag = f"{model}{N}.{mode}.{'chunked' if chunked else 'whole'}"
-            for name, value in (("dense_chunk", 5), ("profile_chunk", 3), ("predictive_subjects", 64), ("predictive_times", 4)):
+            for name, value in (("dense_chunk", 5), ("profile_chunk", 3), ("predictive_subjects", 64), ("predictive_times", 4),
+                                ("bootstrap_chunk", 2), ("bootstrap_subjects", 64), ("npde_subjects", 64), ("vpc_sims", 2),
+                                ("vpc_select", 1)):
                 eng.set_option(name, value if chunked else 0)
             eng.set_params(nn, cond)
             call(tag + ".simulate", lambda: eng.simulate(times))
@@ -105,6 +120,7 @@ def run(lib_path, out_path):
                 penalty_weight=0.2, cov=cov, profiled=True, want=Engine.INFO_OUTPUTS))
             call(tag + ".network_information.cond", lambda: eng.network_information(cond=sets[1]))
             call(tag + ".sensitivity", lambda: eng.sensitivity())
+            call(tag + ".curvature", lambda: eng.curvature())
             call(tag + ".multistart_forward", lambda: eng.multistart_forward(nn_sets, sets))
             call(tag + ".screen_candidates", lambda: eng.screen_candidates(40, 5, candidates))
             call(tag + ".multistart_loss_grad", lambda: eng.multistart_loss_grad(nn_sets, sets))
@@ -117,6 +133,18 @@ def run(lib_path, out_path):
                 call(tag + f".fit_conditional.spec{spec}", lambda: eng.fit_conditional(-4.0, 3.0, 11, 9, 0.1, -0.5))
             call(tag + ".refine_conditional", lambda: eng.refine_conditional(max_evals=8, penalty_weight=0.1, penalty_center=-0.5))
             call(tag + ".refine_conditional.x0", lambda: eng.refine_conditional(x0=sets[2], max_evals=8))
+            eng.set_params(nn, cond)
+            eng.set_rng(4242, 0)
+            call(tag + ".bootstrap_conditional.noise", lambda: eng.bootstrap_conditional(
+                sigma, B, ranks=[0, 4, 8], noise=boot_noise, max_evals=8, penalty_weight=0.1, penalty_center=-0.5, want_replicates=True))
+            call(tag + ".bootstrap_conditional.draws", lambda: eng.bootstrap_conditional(
+                sigma, B, center=sets[1], first_rep=5, max_evals=8, want_replicates=True))
+            call(tag + ".bootstrap_noise", lambda: eng.bootstrap_noise(5, B))
+            call(tag + ".npde.given", lambda: eng.npde(sigma, B, sim_sets, noise=sim_noise, want_sims=True))
+            call(tag + ".npde.draws", lambda: eng.npde(sigma, B, prior_mean=-0.6, prior_sd=0.9, first_rep=3, want_sims=True))
+            call(tag + ".npde_draws", lambda: eng.npde_draws(3, B))
+            call(tag + ".vpc.given", lambda: eng.vpc(sigma, B, sim_sets, noise=sim_noise, groups=groups, n_groups=3))
+            call(tag + ".vpc.draws", lambda: eng.vpc(sigma, B, prior_mean=-0.6, prior_sd=0.9, first_rep=3, groups=groups, n_groups=3))
             if chunked:
                 continue
             for gamma in (1.0, 0.35):
